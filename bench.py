@@ -7,6 +7,19 @@ once (cnn_gp.gram.ModelKern.bind; the reference recomputes them per tile and sid
 every Gram tile of this rank evaluated in place into a device-resident Kxx.
 
     python bench.py [--gpus N --steps K --warmup W] [--config C --n N --tile B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it sets up, runs W warm-up steps,
+times K steps, writes its outputs if asked to and prints the line (metric, value, unit,
+higher_is_better, dtype, steps, ms_per_step = the wall-clock milliseconds of one timed
+step, ...).  --full adds every other leg listed below; without it each of them is off, as
+if its --no-* switch were given, and no full-result file is written.
+
+--dump-outputs DIR writes what the last timed step left in Kxx, as DIR/kxx_diag.npy (the
+n diagonal entries) and DIR/kxx_upper.npy (every entry i <= j when there are at most 2^22
+of them, else a fixed sample of 2^22 of them, numpy default_rng(0)), in the run's dtype
+(float64 or float32).  The images are torch.rand of a CPU generator seeded 0, so two runs
+with the same arguments dump the same entries of the same problem.  One rank only.
 
 --gpus N > 1 without a torchrun environment: this process does no GPU work, starts
 ``python -m torch.distributed.run --nproc-per-node N ... bench.py <same args>`` as a
@@ -21,9 +34,10 @@ mirrors; K[i, i] comes from the per-image variance chain).  The reference's sche
 would count B² for a diagonal tile; that figure is reported as
 ``reference_schedule_pairs_per_s`` beside it.
 
-Also on the same JSON line, in this order (each in its own slot; a leg that fails records
-{"error": ...} there and the line still prints; the line is compact_line() of the full
-result, which is written to gpurun_out/bench_full.json — DESIGN.md §6 defines each leg):
+With --full, also on the same JSON line, in this order (each in its own slot; a leg that
+fails records {"error": ...} there and the line still prints; the line is compact_line()
+of the full result, which is written to the file the line names as ``full_result``,
+CGP_BENCH_FULL_OUT if set — DESIGN.md §6 defines each leg):
   roofline           the whole-network kernel (net_kernel, fp64 VALU-bound): credited
                      direct-stencil flops vs the fp64 peak, the issued fp64 flops and the
                      VALU issue fraction and HBM traffic from the committed PMC passes
@@ -91,6 +105,10 @@ PMC_FILES = [os.path.join(ROOT, "profiles", r, "net_pmc.json") for r in ("r6", "
 FLOPS_FILES = [os.path.join(ROOT, "profiles", r, "flops_pmc.json") for r in ("r6", "r5")]
 CALIB_FILES = [os.path.join(ROOT, "profiles", r, "cpu_calibration.json") for r in ("r4", "r2")]
 DIST_TIMEOUT_S = float(os.environ.get("CGP_DIST_TIMEOUT_S", "120"))
+# the switches a run without --full sets: every leg but the headline
+PLAIN_RUN_OFF = ("no_probe", "no_solve", "no_cpu", "no_second", "no_cifar10", "no_f32",
+                 "no_dropin", "no_fullscale", "no_fullscale_f32", "no_fullscale_cifar10")
+DUMP_MAX_ENTRIES = 1 << 22     # --dump-outputs: 32 MB of float64 in kxx_upper.npy
 
 
 def parse(argv=None):
@@ -102,6 +120,12 @@ def parse(argv=None):
     p.add_argument("--n", type=int, default=4096, help="Kxx size at world size 1")
     p.add_argument("--tile", type=int, default=1024)
     p.add_argument("--dtype", default="f64", choices=["f64", "f32"])
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, run every other leg (rooflines, CPU baselines, "
+                        "the other configs and precisions, solve, drop-in, full scale) and "
+                        "write the full-result file; the --no-* switches narrow it")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write the Kxx entries of the last timed step to DIR/*.npy")
     p.add_argument("--no-solve", action="store_true")
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--no-probe", action="store_true")
@@ -122,7 +146,13 @@ def parse(argv=None):
     p.add_argument("--fullscale-m", type=int, default=10000)
     p.add_argument("--cpu-seconds", type=float, default=12.0,
                    help="target duration of each CPU-baseline sample")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        for leg in PLAIN_RUN_OFF:
+            setattr(args, leg, True)
+    return args
 
 
 # ------------------------------------------------------------------------------------------
@@ -165,6 +195,8 @@ def launch_or_check(args, argv):
     env_world = os.environ.get("WORLD_SIZE")
     world = args.gpus if env_world is None else int(env_world)
     err = world_error(args.gpus, world, torch.cuda.device_count(), backend)
+    if not err and args.dump_outputs and world != 1:
+        err = "--dump-outputs needs --gpus 1 (each rank holds its own tiles of Kxx only)"
     if err:
         print(f"bench.py: {err}", file=sys.stderr, flush=True)
         return 2
@@ -753,6 +785,30 @@ def build_kxx(mk, model, X, K, tiles, B, n):
             view.copy_(model(xi) if same else model(xi, X[j * B:(j + 1) * B], False, False))
 
 
+def dump_outputs(path, K, n):
+    """--dump-outputs: the Kxx the timed steps built in place (each step overwrites every
+    upper tile, so K holds the last step's entries), as path/<name>.npy in K's dtype.
+    kxx_diag: the n diagonal entries.  kxx_upper: the entries (i, j), i <= j, row-major —
+    all of them when there are at most DUMP_MAX_ENTRIES, else that many drawn with
+    replacement by numpy's default_rng(0).  Strictly-lower off-diagonal tiles are not part
+    of the schedule (they stay NaN) and are never sampled.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if n * (n + 1) // 2 <= DUMP_MAX_ENTRIES:
+        i, j = np.triu_indices(n)
+    else:
+        rng = np.random.default_rng(0)
+        a, b = rng.integers(0, n, (2, DUMP_MAX_ENTRIES))
+        i, j = np.minimum(a, b), np.maximum(a, b)
+    i, j = (torch.from_numpy(np.ascontiguousarray(v)).to(K.device) for v in (i, j))
+    shapes = {}
+    for name, t in (("kxx_diag", K.diagonal()), ("kxx_upper", K[i, j])):
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def dropin_leg(cfg_names, n, tiles, dev, reps=5):
     """exp_mnist_resnet/save_kernel.py:19-29 verbatim in effect: the float32 model
     (config.initial_model.cuda()), host float32 images in a Dataset, and
@@ -945,6 +1001,8 @@ def compact_line(full: dict) -> dict:
     for k in ("error", "watchdog"):
         if full.get(k) is not None:
             line[k] = str(full[k])[:300]
+    if full.get("outputs"):
+        line["outputs"] = full["outputs"]              # --dump-outputs: DIR and each shape
     if full.get("elapsed_s") is not None:
         line["elapsed_s"] = full["elapsed_s"]          # the whole run, rank 0's clock
     line["roofline"] = _pick(full.get("roofline"), _ROOF_KEYS)
@@ -1036,6 +1094,8 @@ def main(argv=None):
     full_path = os.environ.get("CGP_BENCH_FULL_OUT",
                                os.path.join(ROOT, "gpurun_out", "bench_full.json"))
     full["full_result"] = os.path.relpath(full_path, ROOT)
+    if not args.full and "CGP_BENCH_FULL_OUT" not in os.environ:
+        full_path = full["full_result"] = None       # a plain run prints its line only
 
     def make_line(watchdog=False):
         snap = dict(full)
@@ -1072,6 +1132,15 @@ def main(argv=None):
                               tiles_rank0=len(r["tiles"]), pairs_per_step=r["evaluated"])
         full["ranks"] = legs.run("rank_stats", lambda: gather_rank_stats(r["rank_stats"],
                                                                          world, status))
+
+    # --- what the last timed step computed, for output-for-output comparisons ---
+    if not failed and args.dump_outputs:
+        dumped = legs.run("dump_outputs", lambda: dump_outputs(args.dump_outputs, r["K"],
+                                                               n_total), multi_rank=False)
+        if "error" in dumped:
+            full["error"] = dumped["error"]
+        else:
+            full["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
     # --- dominant kernel (timed live in the headline) and the Conv2d stencil alone ---
     if not failed and rank == 0 and probe:
@@ -1190,9 +1259,10 @@ def main(argv=None):
     if rank == 0:
         full["elapsed_s"] = round(deadline.elapsed(), 1)
         try:
-            os.makedirs(os.path.dirname(full_path), exist_ok=True)
-            with open(full_path, "w") as fh:
-                json.dump(full, fh, default=str)
+            if full_path:
+                os.makedirs(os.path.dirname(full_path), exist_ok=True)
+                with open(full_path, "w") as fh:
+                    json.dump(full, fh, default=str)
         except OSError as e:
             print(f"bench.py: could not write {full_path}: {e}", file=sys.stderr)
         dog.stop.set()
@@ -1202,7 +1272,7 @@ def main(argv=None):
             dist.destroy_process_group()
         except Exception:                      # noqa: BLE001 — after a failed leg
             pass
-    return 1 if failed else 0
+    return 1 if failed or "error" in full else 0
 
 
 if __name__ == "__main__":

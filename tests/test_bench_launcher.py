@@ -146,8 +146,60 @@ def test_help_lists_every_leg_switch():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"],
                        capture_output=True, text=True, timeout=120)
     assert p.returncode == 0
-    for flag in ("--no-cifar10", "--no-fullscale", "--no-fullscale-cifar10", "--gpus"):
+    for flag in ("--no-cifar10", "--no-fullscale", "--no-fullscale-cifar10", "--gpus",
+                 "--full", "--dump-outputs"):
         assert flag in p.stdout
+
+
+def test_plain_run_switches_every_other_leg_off():
+    """without --full every leg but the headline is off (each --no-* switch of parse() is
+    in PLAIN_RUN_OFF); --full leaves them to the --no-* switches given"""
+    b = _bench()
+    plain = vars(b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"]))
+    switches = {k for k in plain if k.startswith("no_")}
+    assert switches == set(b.PLAIN_RUN_OFF)
+    assert all(plain[k] for k in switches)
+    assert (plain["steps"], plain["warmup"], plain["full"]) == (7, 2, False)
+    assert plain["dump_outputs"] is None
+    full = vars(b.parse(["--full", "--no-solve"]))
+    assert [k for k in sorted(switches) if full[k]] == ["no_solve"]
+    assert full["full"]
+
+
+def test_dump_outputs_refuses_several_ranks(tmp_path):
+    p = _run_bench(["--gpus", "2", "--dump-outputs", str(tmp_path / "out")],
+                   {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0",
+                    "CGP_BENCH_BACKEND": "gloo"})
+    assert p.returncode == 2, p.stderr
+    assert "--dump-outputs needs --gpus 1" in p.stderr
+    assert p.stdout == "" and not (tmp_path / "out").exists()
+
+
+def test_dump_outputs_sample_is_fixed_and_upper():
+    """past DUMP_MAX_ENTRIES upper entries the dump is a seeded sample: the same entries on
+    every call, all with i <= j (the schedule never writes the strictly-lower tiles)"""
+    import tempfile
+
+    import numpy as np
+    import torch
+    b = _bench()
+    n = 3000                                       # n(n+1)/2 = 4 501 500 > 2^22
+    assert n * (n + 1) // 2 > b.DUMP_MAX_ENTRIES
+    K = torch.arange(n * n, dtype=torch.float32).reshape(n, n)     # K[i, j] = i·n + j, exact
+    got = []
+    for _ in range(2):
+        with tempfile.TemporaryDirectory() as d:
+            shapes = b.dump_outputs(os.path.join(d, "sub"), K, n)
+            assert sorted(os.listdir(os.path.join(d, "sub"))) == ["kxx_diag.npy",
+                                                                  "kxx_upper.npy"]
+            got.append({k: np.load(os.path.join(d, "sub", k + ".npy")) for k in shapes})
+    up, diag = got[0]["kxx_upper"], got[0]["kxx_diag"]
+    assert up.dtype == np.float32 and up.shape == (b.DUMP_MAX_ENTRIES,)
+    assert np.array_equal(up, got[1]["kxx_upper"])
+    i, j = np.divmod(up.astype(np.int64), n)
+    assert (i <= j).all() and len(np.unique(up)) > b.DUMP_MAX_ENTRIES // 2
+    assert np.array_equal(diag, np.arange(n, dtype=np.float32) * (n + 1))
+    assert up.nbytes + diag.nbytes <= 64 << 20
 
 
 def _recorded_full(world=1):

@@ -9,7 +9,7 @@
 #   pytest        the whole GPU suite                     PYTEST_K="-k expr" narrows it
 #   pytest:FILE   one test file (tests/FILE)
 #   smoke         __graft_entry__.smoke()
-#   bench         python bench.py $BENCH_ARGS             (the driver's command by default)
+#   bench         python bench.py $BENCH_ARGS             (every leg by default: --full)
 #   gloo4         CGP_BENCH_BACKEND=gloo bench.py --gpus 4 (the launcher, 4 ranks, 1 GPU)
 #   failleg       bench.py with CGP_BENCH_FAIL_LEG=mnist_as_tf (the line must still print)
 #   tile4096      bench.py --tile 4096 --steps 2 (no OOM in the stencil probe)
@@ -60,25 +60,25 @@ for s in "${LIST[@]}"; do
         step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
         tail -n 1 "$O/smoke.log" ;;
     bench)
-        step bench 1200 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5}
+        step bench 1200 python bench.py ${BENCH_ARGS:---full --steps 20 --warmup 5}
         line "$O/bench.log" ;;
     gloo4)
-        CGP_BENCH_BACKEND=gloo step gloo4 900 python bench.py --gpus 4 --steps 2 --warmup 1 \
+        CGP_BENCH_BACKEND=gloo step gloo4 900 python bench.py --full --gpus 4 --steps 2 --warmup 1 \
             --no-cpu --no-f32 --no-fullscale-f32 --fullscale-n 16384 --cifar10-n 16384 \
             --fullscale-m 4096
         line "$O/gloo4.log" ;;
     failleg)
-        CGP_BENCH_FAIL_LEG=mnist_as_tf step failleg 600 python bench.py --steps 2 \
+        CGP_BENCH_FAIL_LEG=mnist_as_tf step failleg 600 python bench.py --full --steps 2 \
             --warmup 1 --no-cpu --no-f32 --no-fullscale --no-fullscale-cifar10 --no-cifar10
         line "$O/failleg.log" ;;
     tile4096)
-        step tile4096 900 python bench.py --tile 4096 --steps 2 --warmup 1 --no-cpu \
+        step tile4096 900 python bench.py --full --tile 4096 --steps 2 --warmup 1 --no-cpu \
             --no-f32 --no-fullscale --no-fullscale-cifar10 --no-second --no-cifar10 --no-dropin
         line "$O/tile4096.log" ;;
     trace:*)
         cfg=${s#trace:}
         step "trace_$cfg" 600 rocprofv3 --kernel-trace --stats -T -f csv -d "$O/trace_$cfg" \
-            -o trace -- python bench.py --config "$cfg" --steps 3 --no-cpu --no-fullscale \
+            -o trace -- python bench.py --full --config "$cfg" --steps 3 --no-cpu --no-fullscale \
             --no-fullscale-cifar10 --no-second --no-cifar10 --no-f32 --no-dropin
         line "$O/trace_$cfg.log" ;;
     pmc)
