@@ -9,5 +9,7 @@ from .kernels import *  # noqa: F401,F403
 from .data import *  # noqa: F401,F403
 from .kernel_save_tools import *  # noqa: F401,F403
 from .solve import *  # noqa: F401,F403
+from .gram import ntk_kern  # noqa: F401
 
-__all__ = kernels.__all__ + data.__all__ + kernel_save_tools.__all__ + solve.__all__
+__all__ = kernels.__all__ + data.__all__ + kernel_save_tools.__all__ + solve.__all__ + \
+    ("ntk_kern",)

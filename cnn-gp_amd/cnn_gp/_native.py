@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CNNGP_LIB",
                           os.path.join(os.path.dirname(_HERE), "lib", "libcnngp.so"))
 
-CGP_ABI_VERSION = 11
+CGP_ABI_VERSION = 12
 CGP_FLAG_EXACT_RELU = 1
 CGP_FLAG_GENERIC_CONV = 2
 CGP_FLAG_NET_DUAL = 4
@@ -52,6 +52,16 @@ class ReluArgs(ctypes.Structure):
     """Mirror of cgp_relu_args (include/cnngp.h)."""
     _fields_ = [
         ("xy", _vp), ("out", _vp), ("addend", _vp), ("xx", _vp), ("yy", _vp),
+        ("nmaps", _i64), ("n1", _i64), ("n2", _i64),
+        ("hw", _i32), ("same", _i32), ("diag", _i32), ("flags", _i32),
+    ]
+
+
+class ReluNtkArgs(ctypes.Structure):
+    """Mirror of cgp_relu_ntk_args (include/cnngp.h)."""
+    _fields_ = [
+        ("xy", _vp), ("theta", _vp), ("out_xy", _vp), ("out_theta", _vp),
+        ("xx", _vp), ("yy", _vp),
         ("nmaps", _i64), ("n1", _i64), ("n2", _i64),
         ("hw", _i32), ("same", _i32), ("diag", _i32), ("flags", _i32),
     ]
@@ -128,6 +138,9 @@ SIGNATURES = {
     "cgp_conv_f32": (_i32, [ctypes.POINTER(ConvArgs), _vp]),
     "cgp_relu_f64": (_i32, [ctypes.POINTER(ReluArgs), _vp]),
     "cgp_relu_f32": (_i32, [ctypes.POINTER(ReluArgs), _vp]),
+    "cgp_relu_ntk_args_size": (ctypes.c_size_t, []),
+    "cgp_relu_ntk_f64": (_i32, [ctypes.POINTER(ReluNtkArgs), _vp]),
+    "cgp_relu_ntk_f32": (_i32, [ctypes.POINTER(ReluNtkArgs), _vp]),
     "cgp_var_relu_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "cgp_var_relu_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
@@ -196,6 +209,7 @@ def load():
             raise RuntimeError(_lib_err)
         if lib.cgp_conv_args_size() != ctypes.sizeof(ConvArgs) or \
                 lib.cgp_relu_args_size() != ctypes.sizeof(ReluArgs) or \
+                lib.cgp_relu_ntk_args_size() != ctypes.sizeof(ReluNtkArgs) or \
                 lib.cgp_net_op_size() != ctypes.sizeof(NetOp) or \
                 lib.cgp_net_args_size() != ctypes.sizeof(NetArgs) or \
                 lib.cgp_var_op_size() != ctypes.sizeof(VarOp) or \

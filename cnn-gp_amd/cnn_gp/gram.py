@@ -34,7 +34,7 @@ import torch.distributed as dist
 from .data import _ceil_div, _tile_order, tile_schedule
 
 __all__ = ("gram_tiles", "gram_local", "gather_gram", "gram_matrix", "model_kern", "ModelKern",
-           "tile_plan", "tile_cost")
+           "ntk_kern", "tile_plan", "tile_cost")
 
 Tile = Tuple[bool, int, int, int, int]       # (same, i0, j0, rows, cols)
 
@@ -143,6 +143,28 @@ def model_kern(model, device=None, dtype=None) -> ModelKern:
     """kern(x, x2, same) -> device tensor: the model evaluated on the device (a ModelKern:
     the builders below evaluate its tiles from one build's variance maps)."""
     return ModelKern(model, device, dtype)
+
+
+def ntk_kern(model, device=None, dtype=None) -> Callable:
+    """kern(x, x2, same) -> device tensor: the model's neural tangent kernel
+    (NNGPKernel.ntk) of one tile, for gram_tiles / gram_local / gram_strip /
+    classify_distributed in place of model_kern's.  A plain callable, not a ModelKern: the
+    NTK runs layer by layer, so there is no whole-build form to ``bind``.
+
+    save_K calls its kern as kern(x, x2, same, diag) and writes host arrays: called with
+    that fourth argument the tile comes back as a numpy array (save_kernel.py:21-24's
+    kern), so the same object serves save_K as well."""
+    def kern(x, x2, same, diag=None):
+        dev = _default_device(device)
+        xd = x.to(dev, dtype or x.dtype)
+        with torch.no_grad():
+            if same and not diag:
+                th = model.ntk(xd)
+            else:
+                x2d = xd if x2 is x else x2.to(dev, dtype or x2.dtype)
+                th = model.ntk(xd, x2d, bool(same), bool(diag))
+        return th if diag is None else th.detach().cpu().numpy()
+    return kern
 
 
 def _fill_tiles(kern, X, src2, X2, tiles, view):
@@ -308,11 +330,12 @@ def gather_gram(local: torch.Tensor, N: int, N2: Optional[int], batch_size: int,
 
 
 def gram_matrix(model, X, X2=None, batch_size: int = 1024, device=None,
-                dtype=torch.float64, group=None, split: str = "balanced"):
+                dtype=torch.float64, group=None, split: str = "balanced", ntk: bool = False):
     """Full Gram matrix of ``model`` on X (× X2) on the device — single GPU, or sharded
     over the torch.distributed group (one process per GPU: each rank evaluates its tiles
-    into a flat buffer, rank 0 gathers them; other ranks return None)."""
-    kern = model_kern(model, device)
+    into a flat buffer, rank 0 gathers them; other ranks return None).  ``ntk``: the
+    neural tangent kernel (ntk_kern) instead of the NNGP kernel."""
+    kern = ntk_kern(model, device) if ntk else model_kern(model, device)
     N = len(X)
     N2 = None if X2 is None else len(X2)
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:

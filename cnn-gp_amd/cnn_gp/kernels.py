@@ -182,8 +182,10 @@ class NNGPKernel(nn.Module):
             m.__dict__["_cgp_exact_relu"] = bool(enabled)
         return self
 
-    def forward(self, x, y=None, same=None, diag=False):
-        """[N1,C,H,W] × [N2,C,H,W] -> kernel [N1,N2] (or [N1] when diag)."""
+    def _prologue(self, x, y, same, diag):
+        """The argument rules of kernels.py:23-35, the dtype check and the empty-batch
+        result shared by forward and ntk: (y, same, diag, empty) with ``empty`` the result
+        tensor of an empty batch, else None."""
         if y is None:                                            # kernels.py:23-26
             assert same is None
             y = x
@@ -199,24 +201,99 @@ class NNGPKernel(nn.Module):
         diag = bool(diag)
         if x.dtype not in (torch.float32, torch.float64):
             raise TypeError(f"cnn_gp kernels compute in float32 or float64, got {x.dtype}")
-        out_device = x.device
+        empty = None
         if len(x) == 0 or len(y) == 0:
             # the reference's torch ops return the empty [N1, N2] / [N1] result for an empty
             # batch (conv2d on a zero-size batch); there is nothing to evaluate
-            return torch.empty((len(x),) if diag else (len(x), len(y)), dtype=x.dtype,
-                               device=out_device)
+            empty = torch.empty((len(x),) if diag else (len(x), len(y)), dtype=x.dtype,
+                                device=x.device)
+        return y, same, diag, empty
+
+    @staticmethod
+    def _compute_device(x):
         if x.device.type == "cuda":
-            dev = x.device
-        else:
-            if not torch.cuda.is_available():
-                raise RuntimeError("cnn_gp on MI355X needs a HIP device: no GPU is visible "
-                                   "(there is no CPU path)")
-            dev = torch.device("cuda", torch.cuda.current_device())
+            return x.device
+        if not torch.cuda.is_available():
+            raise RuntimeError("cnn_gp on MI355X needs a HIP device: no GPU is visible "
+                               "(there is no CPU path)")
+        return torch.device("cuda", torch.cuda.current_device())
+
+    def forward(self, x, y=None, same=None, diag=False):
+        """[N1,C,H,W] × [N2,C,H,W] -> kernel [N1,N2] (or [N1] when diag)."""
+        y, same, diag, empty = self._prologue(x, y, same, diag)
+        if empty is not None:
+            return empty
+        out_device = x.device
+        dev = self._compute_device(x)
         with torch.cuda.device(dev):
             xd = _to_device(x, dev)
             yd = xd if y is x else _to_device(y.to(x.dtype), dev)
             r = self._run(xd, yd, same, diag, _stream_handle(dev))
         return r.to(out_device) if out_device != dev else r
+
+    def ntk(self, x, y=None, same=None, diag=False, return_nngp=False):
+        """The neural tangent kernel Θ of the model, [N1, N2] (or [N1] when diag); with
+        ``return_nngp`` the pair (K, Θ), K the NNGP kernel ``forward`` gives.  Arguments,
+        dtypes, devices, the empty-batch result and the "not 1x1" error are forward's.
+
+        Θ is the infinite-width kernel of the network trained by gradient descent rather
+        than at initialisation, in the reference's conventions (ReLU without the √2,
+        weight var_weight/k² per tap).  It follows K through the module tree:
+
+            inputs          Θ = 0                        (inputs are not parameters)
+            Conv2d          K' = A(K) + var_bias,  Θ' = A(Θ) + K'   (A: the conv's stencil
+                                                                      without the bias)
+            ReLU            K' as forward,         Θ' = Θ·κ̇,  κ̇ = (π - θ)/2π with
+                            θ = acos(clamp(c·rsqrt(v₁v₂ + f32_tiny), -1, 1)) of the
+                            reference's ReLU (kernels.py:146-151); Θ' = Θ/2 exactly where
+                            the reference overrides K' (same and i = j, or same and diag)
+            Sum / Mixture   the same (weighted) sum on both
+
+        and the result is Θ of the final 1x1 value; a model without a Conv2d gives zeros.
+        Equivalently Θ = Σ over all Conv2d outputs of ⟨∂K_final/∂K_xy^l, K_xy^l⟩ at fixed
+        variances.  Always evaluated layer by layer (program.ntk_steps: the whole-network
+        kernel carries one map); honours set_exact_relu."""
+        y, same, diag, empty = self._prologue(x, y, same, diag)
+        if empty is not None:
+            return (empty, empty.clone()) if return_nngp else empty
+        out_device = x.device
+        dev = self._compute_device(x)
+        with torch.cuda.device(dev):
+            xd = _to_device(x, dev)
+            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
+            k, th = self._run_ntk(xd, yd, same, diag, _stream_handle(dev))
+        if out_device != dev:
+            k, th = k.to(out_device), th.to(out_device)
+        return (k, th) if return_nngp else th
+
+    def _run_ntk(self, x, y, same, diag, stream):
+        n1, c, h, w = x.shape
+        n2 = y.shape[0]
+        plan = self._plan(h, w)
+        if plan.final_hw != (1, 1):                              # kernels.py:53-57
+            raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
+                               " per pair, not 1x1: add a final Conv2d covering the map")
+        sfx = Plan._sfx(x.dtype)
+        lib = N.load()
+        # per-image variances of the inputs (kernels.py:48-49), then of every ReLU's source
+        var0 = torch.empty((n1 + n2, h, w), dtype=x.dtype, device=x.device)
+        N.check(getattr(lib, f"cgp_moments_var_{sfx}")(N.ptr(x), N.ptr(y), n1, n2, c, h * w,
+                                                        N.ptr(var0[:n1]), N.ptr(var0[n1:]),
+                                                        stream), "cgp_moments_var")
+        var = plan.run_variances(var0[:n1], var0[n1:], n1, n2, same, stream,
+                                 need=plan.ntk_need_var())
+        nmaps = n1 if diag else n1 * n2
+        xy0 = torch.empty((nmaps, h, w), dtype=x.dtype, device=x.device)
+        N.check(getattr(lib, f"cgp_moments_xy_{sfx}")(N.ptr(x), N.ptr(y), n1, n2, c, h * w,
+                                                       int(diag), N.ptr(xy0), stream),
+                "cgp_moments_xy")
+        k, th = plan.run_pairs_ntk(xy0, var, n1, n2, same, diag, stream)
+        if th is None:
+            th = torch.zeros_like(k)
+        elif th is k:
+            th = k.clone()
+        shape = (n1,) if diag else (n1, n2)
+        return k.view(shape), th.view(shape)
 
     def _run(self, x, y, same, diag, stream):
         n1, c, h, w = x.shape

@@ -274,6 +274,91 @@ def needed_variances(ops) -> set:
 
 
 # ------------------------------------------------------------------------------------
+# the neural tangent kernel: a second pair map Θ beside K
+# ------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class NtkStep:
+    """One launch of the NTK run.  Buffers are named ("K", value) / ("T", value): the K
+    and Θ maps of an SSA value.
+
+    fn "conv":     dst = A(src)·weight + bias [+ addend]     cgp_conv_* (op.geom; ``bias``
+                   replaces the geometry's: 0 on the Θ stream)
+    fn "relu":     dst = relu(src), variances of value ``var``           cgp_relu_*
+    fn "relu_ntk": dst, dst_theta = relu(src), theta·κ̇                   cgp_relu_ntk_*
+    fn "axpby":    dst = Σ coef·buffer over ``terms`` (coef None: 1)     cgp_axpby_*
+    """
+    fn: str
+    dst: tuple
+    src: Optional[tuple] = None
+    op: Optional[Op] = None
+    bias: float = 0.0
+    addend: Optional[tuple] = None
+    var: Optional[int] = None
+    theta: Optional[tuple] = None
+    dst_theta: Optional[tuple] = None
+    terms: list = dataclasses.field(default_factory=list)
+
+    def reads(self):
+        r = [b for b in (self.src, self.addend, self.theta) if b is not None]
+        return r + [b for _, b in self.terms]
+
+    def writes(self):
+        return [b for b in (self.dst, self.dst_theta) if b is not None]
+
+
+def ntk_steps(prog: Program, v0: int, vf: int):
+    """The launches that carry (K, Θ) through the UNFUSED program: returns (steps, k, theta)
+    with ``k`` = ("K", vf) and ``theta`` the buffer holding Θ of vf, or None for Θ = 0.
+
+    The recursion (the reference's conventions: ReLU without the √2, weight var_weight/k²
+    per tap), with A the conv's constant-weight stencil without the bias:
+
+        input moments   Θ = 0                         (inputs are not parameters)
+        Conv2d          K' = A(K) + var_bias,  Θ' = A(Θ) + K'
+        ReLU            K' = relu(K),          Θ' = Θ·κ̇,  κ̇ = (π - θ)/2π  (1/2 where the
+                        reference overrides K': same and i = j, or same and diag)
+        Sum / Mixture   the same (weighted) sum on both streams
+
+    A zero Θ is carried as None and costs nothing: the first conv's Θ' IS its K' (the same
+    buffer), a ReLU on a value with Θ = 0 is the plain cgp_relu_*, sums skip zero terms
+    (a sum whose only non-zero term has weight 1 passes that term's buffer on)."""
+    steps = []
+    theta = {v0: None}
+    for op in prog.ops:
+        d = op.dst
+        if op.kind == "conv":
+            steps.append(NtkStep("conv", ("K", d), src=("K", op.src), op=op, bias=op.geom.bias))
+            if theta[op.src] is None:
+                theta[d] = ("K", d)
+            else:
+                steps.append(NtkStep("conv", ("T", d), src=theta[op.src], op=op, bias=0.0,
+                                     addend=("K", d)))
+                theta[d] = ("T", d)
+        elif op.kind == "relu":
+            if theta[op.src] is None:
+                steps.append(NtkStep("relu", ("K", d), src=("K", op.src), op=op, var=op.src))
+                theta[d] = None
+            else:
+                steps.append(NtkStep("relu_ntk", ("K", d), src=("K", op.src), op=op,
+                                     var=op.src, theta=theta[op.src], dst_theta=("T", d)))
+                theta[d] = ("T", d)
+        elif op.kind == "add":
+            steps.append(NtkStep("axpby", ("K", d), op=op,
+                                 terms=[(c, ("K", t)) for c, t in op.terms]))
+            live = [(c, theta[t]) for c, t in op.terms if theta[t] is not None]
+            if not live:
+                theta[d] = None
+            elif len(live) == 1 and live[0][0] is None:
+                theta[d] = live[0][1]
+            else:
+                steps.append(NtkStep("axpby", ("T", d), op=op, terms=live))
+                theta[d] = ("T", d)
+        else:
+            raise AssertionError(op.kind)
+    return steps, ("K", vf), theta[vf]
+
+
+# ------------------------------------------------------------------------------------
 # execution
 # ------------------------------------------------------------------------------------
 def _adjacent(x, y) -> bool:
@@ -616,3 +701,94 @@ class Plan:
             for v in [v for v in vals if last.get(v, -1) <= idx and v != op.dst]:
                 del vals[v]
         return vals[self.vf]
+
+    # -- NTK: K and Θ through the unfused program ------------------------------------------
+    def ntk_need_var(self) -> set:
+        """The values whose variance maps the NTK run reads: every ReLU's source in the
+        unfused program (run_variances(need=...))."""
+        return {o.src for o in self.prog.ops if o.kind == "relu"}
+
+    def run_pairs_ntk(self, xy0, var, n1, n2, same, diag, stream):
+        """Runs ntk_steps on the pair maps; returns (K, Θ) of the final value as
+        [nmaps, fh, fw] tensors, Θ None when it is zero (a model without a Conv2d).
+        xy0: the input moments' pair maps [nmaps, H, W] (not modified); var: the variance
+        maps of ntk_need_var().
+
+        Buffers are freed after their last reader, as in run_pairs.  Peak live pair maps:
+        4 on a Conv2d/ReLU chain (K, Θ and K', Θ' of a cgp_relu_ntk_* step; 3 at a conv's
+        Θ launch), plus 2 (K and Θ) for every Sum / Mixture branch result or skip value
+        waiting for its sum -- 6 inside a residual block of the ResNets."""
+        sfx = self._sfx(xy0.dtype)
+        lib = N.load()
+        dev = xy0.device
+        nmaps = n1 if diag else n1 * n2
+        if "_ntk_steps" not in self.__dict__:
+            self._ntk_steps = ntk_steps(self.prog, self.v0, self.vf)
+        steps, kbuf, tbuf = self._ntk_steps
+        last = {}
+        for idx, st in enumerate(steps):
+            for b in st.reads():
+                last[b] = idx
+        last[kbuf] = len(steps)
+        if tbuf is not None:
+            last[tbuf] = len(steps)
+        bufs = {("K", self.v0): xy0}
+
+        def new(op):
+            return torch.empty((nmaps,) + tuple(op.shape_out), dtype=xy0.dtype, device=dev)
+
+        for idx, st in enumerate(steps):
+            op = st.op
+            ho, wo = op.shape_out
+            if st.fn == "conv":
+                out = bufs[st.dst] = new(op)
+                g = op.geom
+                a = N.ConvArgs()
+                a.in_, a.out = N.ptr(bufs[st.src]), N.ptr(out)
+                a.addend = N.ptr(bufs[st.addend]) if st.addend is not None else None
+                a.pre, a.post = N.CGP_PRE_NONE, N.CGP_POST_NONE
+                a.nmaps, a.n1, a.n2 = nmaps, n1, n2
+                (a.h, a.w), a.ho, a.wo = op.shape_in, ho, wo
+                a.taps, a.offset, a.stride, a.dilation = g.taps, g.offset, g.stride, g.dilation
+                a.same, a.diag = int(same), int(diag)
+                a.weight, a.bias = g.weight, st.bias
+                a.flags = self.flags
+                N.check(getattr(lib, f"cgp_conv_{sfx}")(a, stream), "cgp_conv")
+            elif st.fn == "relu":
+                out = bufs[st.dst] = new(op)
+                vx, vy = var[st.var]
+                r = N.ReluArgs()
+                r.xy, r.out, r.addend = N.ptr(bufs[st.src]), N.ptr(out), None
+                r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                r.nmaps, r.n1, r.n2 = nmaps, n1, n2
+                r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
+                r.flags = self.flags
+                N.check(getattr(lib, f"cgp_relu_{sfx}")(r, stream), "cgp_relu")
+            elif st.fn == "relu_ntk":
+                out = bufs[st.dst] = new(op)
+                tout = bufs[st.dst_theta] = new(op)
+                vx, vy = var[st.var]
+                r = N.ReluNtkArgs()
+                r.xy, r.theta = N.ptr(bufs[st.src]), N.ptr(bufs[st.theta])
+                r.out_xy, r.out_theta = N.ptr(out), N.ptr(tout)
+                r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                r.nmaps, r.n1, r.n2 = nmaps, n1, n2
+                r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
+                r.flags = self.flags
+                N.check(getattr(lib, f"cgp_relu_ntk_{sfx}")(r, stream), "cgp_relu_ntk")
+            elif st.fn == "axpby":
+                out = bufs[st.dst] = new(op)
+                n = nmaps * ho * wo
+                for k, (coef, b) in enumerate(st.terms):
+                    c = 1.0 if coef is None else coef
+                    if k == 0:
+                        N.call(f"cgp_axpby_{sfx}", c, N.ptr(bufs[b]), 0.0, None, N.ptr(out), n,
+                               stream)
+                    else:
+                        N.call(f"cgp_axpby_{sfx}", 1.0, N.ptr(out), c, N.ptr(bufs[b]),
+                               N.ptr(out), n, stream)
+            else:
+                raise AssertionError(st.fn)
+            for b in [b for b in bufs if last.get(b, -1) <= idx and b not in st.writes()]:
+                del bufs[b]
+        return bufs[kbuf], (None if tbuf is None else bufs[tbuf])

@@ -630,6 +630,76 @@ __global__ __launch_bounds__(kBlock) void relu_pair_kernel(const ReluP<T> p) {
     }
 }
 
+// ----------------------------------------------------------------------------------
+// ReLU of the NTK recursion on pair maps: K' = relu(K) exactly as relu_pair_kernel writes
+// it, and Theta' = Theta * kdot with kdot = (pi - theta)/(2 pi) the derivative of the
+// arc-cosine map in c at fixed variances, theta from the same t = v1 v2 + tiny as
+// kernels.py:146-151.  Where the reference overrides K' (same and i == j, or same and
+// diag) rho = 1 and Theta' = Theta/2 exactly.  One pass: 3 map reads (K, Theta and the
+// broadcast variances), 2 map writes; every element is read and written by one thread,
+// reads first, so the outputs may alias the inputs (and K may alias Theta).
+// ----------------------------------------------------------------------------------
+template <typename T>
+struct ReluNtkP {
+    const T* xy;
+    const T* theta;
+    T* out_xy;
+    T* out_theta;
+    const T* xx;
+    const T* yy;
+    long long nmaps;
+    FastDiv n2, dhw;
+    int hw, same, diag, exact, mpb;
+};
+
+// exact: the reference's op sequence for theta (correctly rounded 1/sqrt, relu_exact's);
+// else the Newton-refined hardware rsq of the closed-form ReLU.  Every op rounded in T.
+template <typename T>
+__device__ __forceinline__ T relu_kdot(T c, T v1, T v2, int exact) {
+    const T t = v1 * v2 + K<T>::tiny;                       // :146
+    T cs = exact ? c * (T(1) / sqrt_t(t)) : c * rsqrt_fast(t);   // :149
+    cs = cs < T(-1) ? T(-1) : (cs > T(1) ? T(1) : cs);      // clamp(-1, 1), NaN kept
+    return (K<T>::pi - acos_t(cs)) / K<T>::two_pi;          // :151
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void relu_ntk_kernel(const ReluNtkP<T> p) {
+    const long long m0 = (long long)blockIdx.x * p.mpb;
+    long long rem = p.nmaps - m0;
+    const int mb = rem < p.mpb ? (int)rem : p.mpb;
+    const int n = mb * p.hw;
+    const T* src = p.xy + m0 * p.hw;
+    const T* tsrc = p.theta + m0 * p.hw;
+    T* dst = p.out_xy + m0 * p.hw;
+    T* tdst = p.out_theta + m0 * p.hw;
+    T v[kEMax], th[kEMax];
+#pragma unroll
+    for (int k = 0; k < kEMax; ++k) {
+        const int e = threadIdx.x + k * kBlock;
+        v[k] = e < n ? src[e] : T(0);
+        th[k] = e < n ? tsrc[e] : T(0);
+    }
+#pragma unroll
+    for (int k = 0; k < kEMax; ++k) {
+        const int e = threadIdx.x + k * kBlock;
+        if (e < n) {
+            const unsigned ml = fdiv((unsigned)e, p.dhw);
+            const int px = e - (int)ml * p.hw;
+            unsigned i, j;
+            pair_of((unsigned)(m0 + ml), p.n2, p.diag, i, j);
+            const T r = relu_pair(v[k], p.xx, p.yy, i, j, p.hw, px, p.same, p.diag, p.exact);
+            T kd;
+            if (p.same && (p.diag || i == j))
+                kd = T(0.5);                                 // kdot at rho = 1
+            else
+                kd = relu_kdot(v[k], p.xx[(size_t)i * p.hw + px], p.yy[(size_t)j * p.hw + px],
+                               p.exact);
+            dst[e] = r;
+            tdst[e] = th[k] * kd;
+        }
+    }
+}
+
 // ReLU on the per-image variances (kernels.py:154-164)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void var_relu_kernel(const T* __restrict__ xx,
@@ -1335,6 +1405,41 @@ int relu_impl(const cgp_relu_args* a, void* stream) {
 }
 
 template <typename T>
+int relu_ntk_impl(const cgp_relu_ntk_args* a, void* stream) {
+    if (!a || !a->xy || !a->theta || !a->out_xy || !a->out_theta || !a->xx)
+        return fail(CGP_EINVAL, "relu_ntk: NULL argument");
+    if (a->hw <= 0 || a->nmaps <= 0 || a->nmaps >= (1LL << 31))
+        return fail(CGP_EINVAL, "relu_ntk: bad sizes");
+    if (a->n1 <= 0 || a->n2 <= 0 || (a->diag ? a->n1 : a->n1 * a->n2) != a->nmaps)
+        return fail(CGP_EINVAL, "relu_ntk: nmaps inconsistent with n1/n2/diag");
+    if ((a->same || a->diag) && a->n1 != a->n2)
+        return fail(CGP_EINVAL, "relu_ntk: same / diag need n1 == n2");
+    if (!(a->same && a->diag) && !a->yy) return fail(CGP_EINVAL, "relu_ntk: yy is NULL");
+    if (a->hw > kChunkElems)
+        return fail(CGP_EINVAL, "relu_ntk: map of %d pixels too large", a->hw);
+    ReluNtkP<T> p;
+    p.xy = static_cast<const T*>(a->xy);
+    p.theta = static_cast<const T*>(a->theta);
+    p.out_xy = static_cast<T*>(a->out_xy);
+    p.out_theta = static_cast<T*>(a->out_theta);
+    p.xx = static_cast<const T*>(a->xx);
+    p.yy = static_cast<const T*>(a->yy);
+    p.nmaps = a->nmaps;
+    p.n2 = make_fastdiv((unsigned)a->n2);
+    p.dhw = make_fastdiv((unsigned)a->hw);
+    p.hw = a->hw;
+    p.same = a->same;
+    p.diag = a->diag;
+    p.exact = (a->flags & CGP_FLAG_EXACT_RELU) != 0;
+    // relu_impl's chunking: whole maps per workgroup, at most kEMax elements per thread
+    p.mpb = std::max(1, kChunkElems / a->hw);
+    const long long blocks = (a->nmaps + p.mpb - 1) / p.mpb;
+    hipLaunchKernelGGL((relu_ntk_kernel<T>), dim3((unsigned)blocks), dim3(kBlock), 0,
+                       as_stream(stream), p);
+    return check_launch("relu_ntk_kernel");
+}
+
+template <typename T>
 int var_relu_impl(const T* xx, const T* yy, int64_t n1, int64_t n2, int32_t hw, int32_t same,
                   T* xo, T* yo, void* stream) {
     if (!xx || !yy || !xo || !yo) return fail(CGP_EINVAL, "var_relu: NULL argument");
@@ -1520,6 +1625,7 @@ double cgp_net_xvar_scale(void) { return kXVarScale; }
 const char* cgp_last_error(void) { return g_last_error.c_str(); }
 size_t cgp_conv_args_size(void) { return sizeof(cgp_conv_args); }
 size_t cgp_relu_args_size(void) { return sizeof(cgp_relu_args); }
+size_t cgp_relu_ntk_args_size(void) { return sizeof(cgp_relu_ntk_args); }
 size_t cgp_var_op_size(void) { return sizeof(cgp_var_op); }
 size_t cgp_var_args_size(void) { return sizeof(cgp_var_args); }
 int cgp_var_chain_f64(const cgp_var_args* a, void* stream) { return var_chain_impl<double>(a, stream); }
@@ -1581,6 +1687,12 @@ int cgp_relu_f64(const cgp_relu_args* args, void* stream) {
 }
 int cgp_relu_f32(const cgp_relu_args* args, void* stream) {
     return relu_impl<float>(args, stream);
+}
+int cgp_relu_ntk_f64(const cgp_relu_ntk_args* args, void* stream) {
+    return relu_ntk_impl<double>(args, stream);
+}
+int cgp_relu_ntk_f32(const cgp_relu_ntk_args* args, void* stream) {
+    return relu_ntk_impl<float>(args, stream);
 }
 int cgp_var_relu_f64(const double* xx, const double* yy, int64_t n1, int64_t n2, int32_t hw,
                      int32_t same, double* xo, double* yo, void* stream) {

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define CGP_ABI_VERSION 11
+#define CGP_ABI_VERSION 12
 
 /* error codes */
 #define CGP_OK 0
@@ -145,6 +145,33 @@ typedef struct cgp_relu_args {
 } cgp_relu_args;
 int cgp_relu_f64(const cgp_relu_args* args, void* stream);
 int cgp_relu_f32(const cgp_relu_args* args, void* stream);
+
+/*
+ * ABI 12: the ReLU step of the neural tangent kernel recursion (no reference counterpart:
+ * the reference reaches the NTK only through autograd on its torch ops).  Beside the pair
+ * maps xy the recursion carries a second pair map theta; one pass writes
+ *   out_xy    = the map of cgp_relu_* above, the same bits in both ReLU modes;
+ *   out_theta = theta · (π - acos(cos)) / 2π,  cos as above from the same variances —
+ *               the derivative of the ReLU map in xy at fixed variances.
+ * Where cgp_relu_* overrides the map (same && !diag: pairs i == j; same && diag: all),
+ * cos = 1 and out_theta = theta/2 exactly.  With CGP_FLAG_EXACT_RELU cos is evaluated op by
+ * op like the reference's (correctly rounded 1/sqrt); else with the closed form's refined
+ * hardware rsqrt.  In-place (out_xy == xy, out_theta == theta) is allowed, and theta may be
+ * xy itself (the first ReLU after a conv, where theta == xy).  same or diag need n1 == n2.
+ */
+typedef struct cgp_relu_ntk_args {
+    const void* xy;      /* [nmaps][hw] */
+    const void* theta;   /* [nmaps][hw] */
+    void* out_xy;        /* [nmaps][hw] */
+    void* out_theta;     /* [nmaps][hw] */
+    const void* xx;      /* [n1][hw] variances at the ReLU input */
+    const void* yy;      /* [n2][hw] (may be NULL when same && diag) */
+    int64_t nmaps, n1, n2;
+    int32_t hw, same, diag, flags;   /* flags: CGP_FLAG_EXACT_RELU */
+} cgp_relu_ntk_args;
+size_t cgp_relu_ntk_args_size(void);
+int cgp_relu_ntk_f64(const cgp_relu_ntk_args* args, void* stream);
+int cgp_relu_ntk_f32(const cgp_relu_ntk_args* args, void* stream);
 
 /*
  * ReLU on the per-image variances — kernels.py:154-164: xx' = xx/2;
