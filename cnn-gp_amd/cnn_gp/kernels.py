@@ -301,6 +301,15 @@ class NNGPKernel(nn.Module):
         plan = self._plan(h, w)
         sfx = Plan._sfx(x.dtype)
         lib = N.load()
+        if diag and same and VAR_CHAIN and self._net_plan(plan, x.element_size()) is not None:
+            # same and diag: the reference overrides every K' with the image's own variance
+            # (kernels.py:134-165), so the result IS the variance chain's final value — the
+            # launch that fills K[i, i] of a same tile.  Taken from it, the two agree bit for
+            # bit in either precision (the layer pipeline below sums in another order: up to
+            # 2 ulp apart in float32)
+            fused = plan.run_variances_fused(x, x, n1, n1, True, stream, {plan.vf})
+            if fused is not None:
+                return fused[0][plan.vf][0].reshape(n1)
         net = None if diag else self._net_plan(plan, x.element_size())
         if net is not None and VAR_CHAIN:
             # the same launches from a recipe built once per tile shape and stream (record

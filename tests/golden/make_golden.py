@@ -20,6 +20,7 @@ Fixtures (all inputs are float32-representable, stored as float32):
   solve.npz       scipy posv on a reference Kxx with NaN lower triangle
   e2e_mixture.npz Mixture (3 branches, non-zero logits) + 3-term Sum networks at 28x28
                   (whole-network kernel shapes) and 10x10 (layer path), fp64 and fp32
+  e2e_zoo.npz     the networks of tests/net_zoo.py, fp64 Kxx (5 images) and Kxz (5 x 3)
 """
 from __future__ import annotations
 
@@ -301,9 +302,29 @@ def gen_mixture():
     print("mixture:", len(recs), "arrays")
 
 
+def gen_zoo():
+    """The networks of tests/net_zoo.py (outside the reference configs) built from the
+    reference's modules: fp64 Kxx on 5 images and Kxz on 5 x 3 per net."""
+    sys.path.insert(1, os.path.dirname(OUT))
+    import net_zoo
+    recs = {}
+    rng = np.random.default_rng(88)
+    for name, z in net_zoo.zoo(cnn_gp).items():
+        X = uniform(5, z.channels, z.side, rng)
+        Z = uniform(3, z.channels, z.side, rng)
+        model = z.build()
+        Xt, Zt = torch.from_numpy(X).double(), torch.from_numpy(Z).double()
+        recs[f"{name}_X"], recs[f"{name}_Z"] = X, Z
+        with torch.no_grad():
+            recs[f"{name}_Kxx"] = model(Xt).numpy()
+            recs[f"{name}_Kxz"] = model(Xt, Zt, False, False).numpy()
+    np.savez_compressed(os.path.join(OUT, "e2e_zoo.npz"), **recs)
+    print("zoo:", len(recs), "arrays")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["conv", "relu", "e2e", "tiles", "solve", "mixture"]
+    which = sys.argv[1:] or ["conv", "relu", "e2e", "tiles", "solve", "mixture", "zoo"]
     for w in which:
         {"conv": gen_conv_ops, "relu": gen_relu_ops, "e2e": gen_e2e, "tiles": gen_tiles,
-         "solve": gen_solve, "mixture": gen_mixture}[w]()
+         "solve": gen_solve, "mixture": gen_mixture, "zoo": gen_zoo}[w]()

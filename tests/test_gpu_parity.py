@@ -767,6 +767,23 @@ def test_large_tile_properties(cfg, monkeypatch):
     assert float(r) < 1e-6
 
 
+@pytest.mark.parametrize("cfg", CFGS)
+@pytest.mark.parametrize("dt", [torch.float64, torch.float32])
+def test_same_diag_is_the_same_tile_diagonal(cfg, dt):
+    """model(X, X, True, True) of a model on the fused kernel comes from the variance chain,
+    the launch that fills K[i, i] of a same tile: bit-equal in both precisions, and within
+    the layer pipeline's diag path (another summation order) by 1e-13 / RTOL32"""
+    C, side = specs.GEOMETRY[cfg]
+    X = dev(np.random.default_rng(9).random((9, C, side, side)), dt)
+    m = configs_util.model(cfg).to(DEV, dt)
+    with torch.no_grad():
+        d = m(X, X, True, True)
+        assert d.shape == (9,) and torch.equal(torch.diagonal(m(X)), d)
+        lay = m.set_fused_network(False)(X, X, True, True)
+    assert rel_err(d.cpu().numpy(), lay.cpu().numpy()) < (1e-13 if dt == torch.float64
+                                                          else RTOL32)
+
+
 def test_scale_batch_quarters_every_buffer():
     """cgp_scale_batch_f64 (the quartered x-side variance maps of the fp64 net kernel):
     bit-exact alpha·src for many buffers of unequal sizes, empty ones and more than one

@@ -40,7 +40,7 @@ def test_emulated_mixture_and_multiterm_sum():
                        torch.tensor([0.3, -0.2, 0.1])),
         cnn_gp.Sum([cnn_gp.Sequential(), cnn_gp.ReLU(),
                     cnn_gp.Sequential(cnn_gp.ReLU(), cnn_gp.Conv2d(1, var_bias=0.5))]),
-        cnn_gp.ReLU(), cnn_gp.Conv2d(28, padding=0))
+        cnn_gp.ReLU(), cnn_gp.Conv2d(28, padding=0)).double()
     net = NetPlan(Plan(m, 28, 28))
     kinds = [f["kind"] for f, _ in net.records]
     assert kinds.count(3) >= 3                 # LINEAR chain
@@ -48,7 +48,7 @@ def test_emulated_mixture_and_multiterm_sum():
     X = rng.random((3, 1, 28, 28))
     Z = rng.random((2, 1, 28, 28))
     ref = O.kernel(configs_util.spec_of(m), X, Z, False, False)
-    np.testing.assert_allclose(E.kernel(net, X, Z, False), ref, rtol=1e-6)
+    np.testing.assert_allclose(E.kernel(net, X, Z, False), ref, rtol=1e-13)
 
 
 def test_unsupported_programs_fall_back():

@@ -104,6 +104,23 @@ def test_mixture_matches_reference(net):
                                        err_msg=f"{net} {dtn} {name}")
 
 
+def test_zoo_matches_reference():
+    """the networks of tests/net_zoo.py: the oracle, handed the spec of the package's own
+    model, reproduces what the reference computed for the same architecture"""
+    import configs_util
+    import net_zoo
+    z = load("e2e_zoo.npz")
+    assert {k.rsplit("_", 1)[0] for k in z.files} == set(net_zoo.NAMES)
+    for name, net in net_zoo.zoo().items():
+        spec = configs_util.spec_of(net.build())
+        X, Z = z[name + "_X"].astype(np.float64), z[name + "_Z"].astype(np.float64)
+        assert X.shape == (5, net.channels, net.side, net.side)
+        np.testing.assert_allclose(O.kernel(spec, X), z[name + "_Kxx"], rtol=1e-11, atol=0,
+                                   err_msg=name)
+        np.testing.assert_allclose(O.kernel(spec, X, Z, False, False), z[name + "_Kxz"],
+                                   rtol=1e-11, atol=0, err_msg=name)
+
+
 @pytest.mark.parametrize("cfg", ["mnist_paper_convnet_gp", "mnist_as_tf"])
 def test_torch_cpu_baseline_matches_reference(cfg):
     """bench.py's CPU baseline (oracle/torch_cpu.py) computes what the reference does"""
