@@ -27,6 +27,7 @@ CGP_NET_CODE_SUM = 0x200         # conv: outputs summed for the next op's reduct
 CGP_NET_CODE_FROM_SUM = 0x400    # reduction: reads the previous conv's partial sums
 CGP_NET_CODE_GEOMETRY = 0xff
 CGP_VAR_MOMENTS, CGP_VAR_CONV, CGP_VAR_HALF, CGP_VAR_SUM = 0, 1, 2, 3
+CGP_VAR_FORM_SCALED, CGP_VAR_FORM_RSQRT = 0, 1   # cgp_net_var_form()
 
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
@@ -125,6 +126,7 @@ def make_fastdiv(d: int):
 SIGNATURES = {
     "cgp_abi_version": (_i32, []),
     "cgp_net_xvar_scale": (ctypes.c_double, []),
+    "cgp_net_var_form": (_i32, []),
     "cgp_last_error": (ctypes.c_char_p, []),
     "cgp_conv_args_size": (ctypes.c_size_t, []),
     "cgp_relu_args_size": (ctypes.c_size_t, []),
@@ -146,6 +148,7 @@ SIGNATURES = {
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_axpby_f32": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_scale_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _f64, _vp]),
+    "cgp_rsqrt_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _vp]),
     "cgp_cast_f32_f64": (_i32, [_vp, _vp, _i64, _vp]),
     "cgp_transpose_f64": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "cgp_chol_solve_f64": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _f64,

@@ -7,6 +7,7 @@ storage only: no torch compute runs on the pair maps.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Optional
 
@@ -36,14 +37,16 @@ def _to_device(t: torch.Tensor, device) -> torch.Tensor:
 
 class _ImageVariances:
     """Variance maps of one image set for one Gram build (NNGPKernel.image_variances):
-    var[v] = [N, h, w] maps of every value the whole-network kernel reads, qvar[v] their
-    x-side copies scaled by cgp_net_xvar_scale() = 1/16 (fp64 closed-form ReLU), key =
-    (H, W, dtype, plan flags)."""
+    var[v] = [N, h, w] maps of every value the whole-network kernel reads, and what the
+    library's fp64 closed-form ReLU reads in their place (cgp_net_var_form): qvar[v], their
+    x-side copies scaled by cgp_net_xvar_scale() = 1/16, or mvar[v], the 1/sqrt(v/8) maps
+    that serve the set on either side of a tile; key = (H, W, dtype, plan flags)."""
 
-    __slots__ = ("images", "var", "qvar", "key")
+    __slots__ = ("images", "var", "qvar", "mvar", "key")
 
-    def __init__(self, images, var, qvar, key):
+    def __init__(self, images, var, qvar, key, mvar=None):
         self.images, self.var, self.qvar, self.key = images, var, qvar, key
+        self.mvar = mvar or {}
 
     def __len__(self):
         return len(self.images)
@@ -320,11 +323,12 @@ class NNGPKernel(nn.Module):
             # every variance map in one launch (cgp_var_chain_*), scaled (1/16) x-side copies
             # included (kernels.py:44-49 moments, then the program on each image)
             fused = plan.run_variances_fused(x, y, n1, n2, same, stream, net.need_var,
-                                             net.quarter_vars(x.dtype, plan.flags),
+                                             net.chain_quarter(x.dtype, plan.flags),
                                              views=False)
             if fused is not None:
                 var, qvar = fused
-                return net.run(x, y, var, n1, n2, same, stream, plan.flags, qvar=qvar)
+                return net.run(x, y, var, n1, n2, same, stream, plan.flags,
+                               qvar=qvar or None)
         # per-image variances of the inputs (kernels.py:48-49)
         var0 = torch.empty((n1 + n2, h, w), dtype=x.dtype, device=x.device)
         N.check(getattr(lib, f"cgp_moments_var_{sfx}")(N.ptr(x), N.ptr(y), n1, n2, c, h * w,
@@ -371,24 +375,36 @@ class NNGPKernel(nn.Module):
         net = self._net_plan(plan, x.element_size())
         if net is None:
             return None
-        quarter = net.quarter_vars(x.dtype, plan.flags)
+        quarter = net.chain_quarter(x.dtype, plan.flags)
         chain = plan._var_chain(set(net.need_var), set(quarter) & set(net.need_var), x.device)
         if chain is None:
             return None
-        size = n * (chain["total"] + chain["qtotal"]) * x.element_size()
+        # the rsqrt form's 1/sqrt(v/8) maps take the place of the scaled copies
+        roots = net.root_elems(x.dtype, plan.flags)
+        size = n * (chain["total"] + chain["qtotal"] + roots) * x.element_size()
         if max_bytes is None:
             max_bytes = torch.cuda.mem_get_info(x.device)[0] // 4
         if size > max_bytes:
             return None
         x = x.contiguous()
+        mvar = {}
         with torch.cuda.device(x.device):
-            fused = plan.run_variances_fused(x, x, n, n, True, _stream_handle(x.device),
-                                             net.need_var, quarter)
+            stream = _stream_handle(x.device)
+            fused = plan.run_variances_fused(x, x, n, n, True, stream, net.need_var, quarter)
+            if fused is not None and roots:
+                # one launch on the same stream, after the chain that writes the plain maps
+                used = sorted(net.quarter_vars(x.dtype, plan.flags))
+                mvar = {v: torch.empty_like(fused[0][v][0]) for v in used}
+                k = len(used)
+                N.call("cgp_rsqrt_batch_f64", k,
+                       (ctypes.c_void_p * k)(*[fused[0][v][0].data_ptr() for v in used]),
+                       (ctypes.c_void_p * k)(*[mvar[v].data_ptr() for v in used]),
+                       (ctypes.c_int64 * k)(*[mvar[v].numel() for v in used]), stream)
         if fused is None:
             return None
         var, qvar = fused
         return _ImageVariances(x, {v: xx for v, (xx, _) in var.items()}, dict(qvar),
-                               (h, w, x.dtype, plan.flags, self._weights_version()))
+                               (h, w, x.dtype, plan.flags, self._weights_version()), mvar)
 
     def tile_from_variances(self, vx: "_ImageVariances", i0: int, i1: int,
                             vy: "_ImageVariances", j0: int, j1: int, same: bool,
@@ -418,9 +434,10 @@ class NNGPKernel(nn.Module):
         x, y = vx.images[i0:i1], vy.images[j0:j1]
         var = {v: (m[i0:i1], vy.var[v][j0:j1]) for v, m in vx.var.items()}
         qvar = {v: q[i0:i1] for v, q in vx.qvar.items()}
+        mvar = {v: (m[i0:i1], vy.mvar[v][j0:j1]) for v, m in vx.mvar.items()}
         with torch.cuda.device(x.device):
             return net.run(x, y, var, i1 - i0, j1 - j0, same, _stream_handle(x.device),
-                           flags, out=out, qvar=qvar or None)
+                           flags, out=out, qvar=qvar or None, mvar=mvar or None)
 
     def layers(self):
         return 0

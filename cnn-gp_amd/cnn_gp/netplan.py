@@ -709,10 +709,14 @@ class NetPlan:
         return (nbi * (nbi + 1) // 2 if same else nbi * nbj) * st * st
 
     def prepare(self, x, y, var, n1: int, n2: int, same: bool, flags: int = 0,
-                out: Optional[torch.Tensor] = None, qvar: Optional[dict] = None):
+                out: Optional[torch.Tensor] = None, qvar: Optional[dict] = None,
+                mvar: Optional[dict] = None):
         """Upload the op lists for these variance maps; return (launch(stream), out).
-        ``qvar``: the scaled (1/16) x-side maps (program.Plan.run_variances_fused), else they
-        are filled here with cgp_scale_batch_f64.
+        ``var`` holds plain variances.  What the fp64 closed-form ReLU reads instead is the
+        library's choice (var_form()): scaled (1/16) x-side maps, taken from ``qvar``
+        (program.Plan.run_variances_fused) or filled here with cgp_scale_batch_f64; or
+        1/sqrt(v/8) maps of both sides, taken from ``mvar`` (value -> (x side, y side),
+        NNGPKernel.image_variances) or filled here with cgp_rsqrt_batch_f64.
         ``out`` may be a row-strided view (e.g. a tile of a larger K): the kernel writes
         K[i, j] at out[i * out.stride(0) + j]."""
         sfx = "f64" if x.dtype == torch.float64 else "f32"
@@ -733,12 +737,36 @@ class NetPlan:
         fn = getattr(lib, f"cgp_net_{sfx}")
         launches = []
         keep = []
-        # the fp64 closed-form ReLU (csrc/cgp_common.h relu_q_n) reads the x-side variance
-        # maps scaled by cgp_net_xvar_scale() = 1/16 (an exact scaling that folds its Newton
-        # steps' halvings); the copies are filled on the launch stream before the kernels
+        # the fp64 closed-form ReLU (csrc/cgp_common.h relu_q_n) reads derived maps in place
+        # of the variances, in the form the library names (var_form()); they are filled on
+        # the launch stream before the kernels.  Scaled form: the x-side maps times
+        # cgp_net_xvar_scale() = 1/16 (an exact scaling that folds its Newton steps' halvings)
         quarters = []
+        roots = []                             # (plain map, m map, elements)
         used = self.quarter_vars(x.dtype, flags)
-        if used:
+        plain = var                            # kdiag stays the plain final variance
+        rsqrt_form = bool(used) and self.var_form() == N.CGP_VAR_FORM_RSQRT
+        if rsqrt_form:
+            # the one-root closed form reads m = 1/sqrt(v/8) on both sides
+            # (cgp_rsqrt_batch_f64): one map set per image set, written on the launch
+            # stream before the kernels unless the caller holds them already (``mvar``)
+            var = dict(var)
+            shapes = self.plan.prog.shapes
+            for v in sorted(used):
+                if mvar is not None:
+                    var[v] = mvar[v]
+                    continue
+                vx, vy = var[v]
+                hw = shapes[v][0] * shapes[v][1]
+                mx = torch.empty((n1 * hw,), dtype=x.dtype, device=x.device)
+                roots.append((vx, mx, n1 * hw))
+                my = mx
+                if vy.data_ptr() != vx.data_ptr() or n1 != n2:
+                    my = torch.empty((n2 * hw,), dtype=x.dtype, device=x.device)
+                    roots.append((vy, my, n2 * hw))
+                keep += [mx, my]
+                var[v] = (mx, my)
+        elif used:
             var = dict(var)
             for v in sorted(used):
                 vx, vy = var[v]
@@ -774,7 +802,7 @@ class NetPlan:
             a = N.NetArgs()
             a.x, a.y, a.out = x.data_ptr(), y.data_ptr(), out.data_ptr()
             if same:
-                a.kdiag = var[self.plan.vf][0].data_ptr()
+                a.kdiag = plain[self.plan.vf][0].data_ptr()
             a.ops = ops_dev.data_ptr() + offs[sidx]    # records are 8-byte aligned
             a.n1, a.n2, a.ldo = n1, n2, out.stride(0)
             a.nops, a.channels, a.h, a.w = st.n_ops, x.shape[1], x.shape[2], x.shape[3]
@@ -794,10 +822,17 @@ class NetPlan:
             q_src = (ctypes.c_void_p * nq)(*[N.ptr(s_) for s_, _ in quarters])
             q_dst = (ctypes.c_void_p * nq)(*[N.ptr(q_) for _, q_ in quarters])
             q_n = (ctypes.c_int64 * nq)(*[s_.numel() for s_, _ in quarters])
+        if roots:      # likewise every 1/sqrt(v/8) map
+            nr = len(roots)
+            r_src = (ctypes.c_void_p * nr)(*[s_.data_ptr() for s_, _, _ in roots])
+            r_dst = (ctypes.c_void_p * nr)(*[m_.data_ptr() for _, m_, _ in roots])
+            r_n = (ctypes.c_int64 * nr)(*[n_ for _, _, n_ in roots])
 
         def run_all(stream):
             if quarters:
                 N.call("cgp_scale_batch_f64", nq, q_src, q_dst, q_n, xscale, stream)
+            if roots:
+                N.call("cgp_rsqrt_batch_f64", nr, r_src, r_dst, r_n, stream)
             for u0 in range(0, units, chunk):
                 u1 = min(units, u0 + chunk)
                 for a in launches:
@@ -832,9 +867,10 @@ class NetPlan:
         return launch, out
 
     def quarter_vars(self, dtype, flags: int = 0) -> set:
-        """Values whose x-side variance maps the fp64 closed-form ReLU reads quartered."""
-        # the fp64 closed-form ReLU (relu_q_n) reads its x-side maps scaled by
-        # cgp_net_xvar_scale() = 1/16 ("quarter": the round-2 name of the 1/4 scale)
+        """Values whose variance maps the fp64 closed-form ReLU reads in a derived form
+        (var_form(): the x-side maps quartered, or 1/sqrt(v/8) maps on both sides)."""
+        # scaled form: relu_q_n reads its x-side maps scaled by cgp_net_xvar_scale() = 1/16
+        # ("quarter": the round-2 name of the 1/4 scale)
         if dtype != torch.float64 or flags & N.CGP_FLAG_EXACT_RELU:
             return set()
         used = self.__dict__.get("_quarter_used")
@@ -845,6 +881,32 @@ class NetPlan:
                 used |= {f["var2"] for f, _ in st.records if "var2" in f}
             self.__dict__["_quarter_used"] = used
         return set(used)
+
+    @staticmethod
+    def var_form() -> int:
+        """The maps the library's fp64 closed-form ReLU reads (cgp_net_var_form):
+        CGP_VAR_FORM_SCALED (x side v/16, y side v) or CGP_VAR_FORM_RSQRT (1/sqrt(v/8) on
+        both sides).  Asked, never assumed: a two-root build of the library runs through
+        the same host code."""
+        return N.load().cgp_net_var_form()
+
+    def chain_quarter(self, dtype, flags: int = 0) -> set:
+        """The values whose scaled x-side copies the variance chain writes for this
+        library's closed form: quarter_vars in the scaled form, none in the rsqrt form
+        (its maps come from cgp_rsqrt_batch_f64, from the plain ones)."""
+        used = self.quarter_vars(dtype, flags)
+        if used and self.var_form() == N.CGP_VAR_FORM_RSQRT:
+            return set()
+        return used
+
+    def root_elems(self, dtype, flags: int = 0) -> int:
+        """Elements per image of the 1/sqrt(v/8) maps the rsqrt form holds (0 in the
+        scaled form): what a bind or a recipe allocates on top of the chain's output."""
+        used = self.quarter_vars(dtype, flags)
+        if not used or self.var_form() != N.CGP_VAR_FORM_RSQRT:
+            return 0
+        shapes = self.plan.prog.shapes
+        return sum(shapes[v][0] * shapes[v][1] for v in used)
 
     def tile_recipe(self, plan, x, y, n1: int, n2: int, same: bool, flags: int, stream):
         """The cached TileRecipe of a forward of this shape on ``stream`` (built on first
@@ -869,10 +931,11 @@ class NetPlan:
             return rec
 
     def run(self, x, y, var, n1: int, n2: int, same: bool, stream, flags: int = 0,
-            out: Optional[torch.Tensor] = None, qvar: Optional[dict] = None):
+            out: Optional[torch.Tensor] = None, qvar: Optional[dict] = None,
+            mvar: Optional[dict] = None):
         """K tile [n1, n2] of the pairs (x_i, y_j).  var: value -> (xx [n1,..], yy [n2,..])
         for every value in ``need_var``."""
-        launch, out = self.prepare(x, y, var, n1, n2, same, flags, out, qvar)
+        launch, out = self.prepare(x, y, var, n1, n2, same, flags, out, qvar, mvar)
         launch(stream)
         return out
 
@@ -898,7 +961,7 @@ class TileRecipe:
     def build(cls, net, plan, x, y, n1, n2, same, flags, stream):
         from .program import DevPtr
         need = set(net.need_var)
-        quarter = net.quarter_vars(x.dtype, flags) & need
+        quarter = net.chain_quarter(x.dtype, flags) & need
         chain = plan._var_chain(need, quarter, x.device)
         if chain is None or chain["lds"] * x.element_size() > 64 * 1024 or \
                 x.shape[2] * x.shape[3] > 1024:
@@ -907,12 +970,14 @@ class TileRecipe:
         n = n1 + m2
         item = x.element_size()
         vbytes = (n * chain["total"] + n1 * chain["qtotal"]) * item
+        # the rsqrt form's maps (prepare allocates them): one set per image of either side
+        mbytes = n * net.root_elems(x.dtype, flags) * item
         units = net.units(n1, n2, same)
         sbytes = sum(units * st.load_stride for st in net.stages[1:]) * item
-        if vbytes + sbytes > RECIPE_MAX_BYTES:
+        if vbytes + mbytes + sbytes > RECIPE_MAX_BYTES:
             return None
         r = cls()
-        r.nbytes = vbytes + sbytes
+        r.nbytes = vbytes + mbytes + sbytes
         r.shape = (n1, n2, tuple(x.shape[1:]), x.dtype, x.device)
         r.same = bool(same)
         r.vbuf = torch.empty((vbytes // item,), dtype=x.dtype, device=x.device)

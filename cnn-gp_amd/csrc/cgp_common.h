@@ -163,14 +163,32 @@ __device__ __forceinline__ float fma_t(float a, float b, float c) {
 // v_fma_f64 with an SGPR-pair operand and the table lives in SGPRs only while in use.
 // P̃(x4) = P(x4/4)/16: coefficient k scaled by 1/(16·4^k), exact powers of two, so Horner in
 // x4 = 4x rounds exactly like Horner in x (relu_q_n)
-// x-side variance maps the fp64 closed form reads: v/16 (exact; ABI 9, cgp_net_xvar_scale).
+// x-side variance maps the two-root fp64 closed form reads: v/16 (exact; ABI 9,
+// cgp_net_xvar_scale; the one-root form's maps are var_rsqrt8 below).
 // Its Newton step then yields y = 8/sqrt(t), so u = 4x = 2 - |c/4|·y is one fma with source
 // modifiers, sqrt(t)/2 comes out of the same step and the polynomial's coefficients carry
 // the factor 2 back (exact).  Rounds 2-3 read v/4 and needed a multiply and a min for u:
 // one op more per pixel, measured 0.9-1.4% slower on all three configs
 // (profiles/r4/ab_r4m_xvar_scale.log)
 constexpr double kXVarScale = 0.0625;
-constexpr double kPolyQ = 0.125;   // P̃(x4) = P(x4/4)·kPolyQ·4^-k per coefficient
+// CGP_RELU_ONE_ROOT=1 (default, round 7): the fp64 closed form reads m = 1/sqrt(v/8) maps on
+// both sides and takes one v_rsq_f64 per pixel (relu_q_n below); its polynomial term is
+// x4²·R·P̃(x4) with P̃ = P/2.  0: the two-root form on (v/16, v) maps, P̃ = P/8.
+#ifndef CGP_RELU_ONE_ROOT
+#define CGP_RELU_ONE_ROOT 1
+#endif
+// which maps the fp64 closed form reads (cgp_net_var_form, include/cnngp.h)
+constexpr int kNetVarForm = CGP_RELU_ONE_ROOT ? CGP_VAR_FORM_RSQRT : CGP_VAR_FORM_SCALED;
+constexpr double kPolyQ = CGP_RELU_ONE_ROOT ? 0.5 : 0.125;   // P̃(x4) = P(x4/4)·kPolyQ·4^-k per coefficient
+// m = 1/sqrt(v/8) of the one-root form: v/8 is exact, sqrt and the division are correctly
+// rounded (the maps are written once per bind, so the slow ops cost nothing), +inf at v = 0.
+// The one producer of every m map: the maps of a bound build, a per-tile forward and the
+// layer-variance path are then bit-identical
+__device__ __forceinline__ double var_rsqrt8(double v) { return 1.0 / __builtin_sqrt(v * 0.125); }
+// Y = m1·m2 is capped at 2^66 = 8/sqrt(f32_tiny): a pixel with a zero variance on either
+// side (m = +inf), or a product that overflows, sees exactly t = tiny, the reference's
+// `+ f32_tiny` (kernels.py:146); for t >= 1e-22 that addend is below fp64 rounding
+constexpr double kYMax = 0x1p66;
 constexpr double poly_q(int k) {
     double v = kReluPolyD[k] * kPolyQ;
     for (int n = 0; n < k; ++n) v *= 0.25;
@@ -297,6 +315,8 @@ __device__ __forceinline__ void relu_fast_n(double (&c)[R], const double (&v1)[R
     for (int r = 0; r < R; ++r)
         c[r] = __builtin_fma(sx[r], p[r], (c[r] + __builtin_fabs(c[r])) * 0.25);
 }
+// (The two-root form, CGP_RELU_ONE_ROOT=0; the default one-root form, which reads 1/sqrt(v/8)
+// maps and shares everything from the vote on, is described in relu_q_n's body.)
 // The map of relu_fast_n in the form the whole-network kernel runs (28 VALU ops + 2 rsq
 // per pixel instead of 31): every 1/2 of the two Newton steps and the output's 1/4 is
 // folded into a power-of-two scaling of an input or a coefficient, so each Newton step
@@ -352,7 +372,32 @@ template <int R, bool QIN, int AD = 0>
 __device__ __forceinline__ void relu_q_n(double (&c)[R], const double (&v1q)[R],
                                          const double (&v2)[R], const PolyTab& tab,
                                          unsigned long long seg = ~0ull) {
-    double y[R], st[R], sx[R], u[R], p[R];   // u: x4
+    double sx[R], u[R], p[R];   // u: x4
+#if CGP_RELU_ONE_ROOT
+    // One root per pixel.  v1q, v2 hold m = 1/sqrt(v/8) of the two sides, so Y = m1·m2 =
+    // 8/sqrt(t) is one multiply (no estimate, no Newton step) and x4 = 2 − |cq|·Y as in the
+    // two-root form.  sqrt(t) and sqrt(x) are never needed by themselves: with
+    // z = x4·Y² = 256·x/t, sqrt(t)·x^1.5 = x²·sqrt(t/x) = x4²·R/2 where R = r·(3 − z·r·r) =
+    // 2/sqrt(z), r = rsq(z), is the one refined root; the 1/2 is in P̃ (kPolyQ).
+    // 13 + D VALU ops and one v_rsq_f64 per pixel against 14 + D and two.
+    double Y[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if constexpr (!QIN) c[r] *= 0.25;
+        Y[r] = __builtin_fmin(v1q[r] * v2[r], kYMax);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        // u = 2 - 2|rho| in one rounding, floored at 2^-51 (|rho| <= 1 - 2^-52, above)
+        u[r] = __builtin_fmax(__builtin_fma(-__builtin_fabs(c[r]), Y[r], 2.0), 2.0 - 2.0 * kRhoMax);
+        const double z = (u[r] * Y[r]) * Y[r];
+        const double h = __builtin_amdgcn_rsq(z);
+        const double m = z * h;
+        const double R2 = h * __builtin_fma(-m, h, 3.0);   // 2/sqrt(z) = sqrt(t/x)/8
+        sx[r] = (u[r] * u[r]) * R2;
+    }
+#else
+    double y[R], st[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if constexpr (!QIN) c[r] *= 0.25;
@@ -372,6 +417,7 @@ __device__ __forceinline__ void relu_q_n(double (&c)[R], const double (&v1q)[R],
         const double sq4 = m * __builtin_fma(-m, h, 3.0);
         sx[r] = (st[r] * u[r]) * sq4;
     }
+#endif
     if constexpr (AD == 2) {
         const unsigned long long ex = __builtin_amdgcn_read_exec() & seg;
         auto all_seg = [&](bool pred) { return (__ballot(pred) & seg) == ex; };

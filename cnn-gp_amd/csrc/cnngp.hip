@@ -794,6 +794,16 @@ __global__ __launch_bounds__(kBlock) void scale_batch_kernel(ScaleBatch b, doubl
     for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride)
         dst[e] = alpha * src[e];
 }
+// dst_k = 1/sqrt(src_k / 8): the maps the one-root fp64 closed form reads (var_rsqrt8)
+__global__ __launch_bounds__(kBlock) void rsqrt_batch_kernel(ScaleBatch b) {
+    const int k = blockIdx.y;
+    const double* __restrict__ src = b.src[k];
+    double* __restrict__ dst = b.dst[k];
+    const long long n = b.n[k];
+    const long long stride = (long long)gridDim.x * kBlock;
+    for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride)
+        dst[e] = var_rsqrt8(src[e]);
+}
 
 __global__ __launch_bounds__(kBlock) void cast_kernel(const float* __restrict__ in,
                                                       double* __restrict__ out, long long n) {
@@ -1726,6 +1736,31 @@ int cgp_scale_batch_f64(int32_t count, const double* const* src, double* const* 
         hipLaunchKernelGGL(scale_batch_kernel, dim3(grid_for(most), m), dim3(kBlock), 0,
                            as_stream(stream), b, alpha);
         const int rc = check_launch("scale_batch_kernel");
+        if (rc != CGP_OK) return rc;
+    }
+    return CGP_OK;
+}
+int cgp_rsqrt_batch_f64(int32_t count, const double* const* src, double* const* dst,
+                        const int64_t* n, void* stream) {
+    if (count < 0 || (count > 0 && (!src || !dst || !n)))
+        return fail(CGP_EINVAL, "rsqrt_batch: bad arguments");
+    for (int k = 0; k < count; ++k)   // every buffer before the first launch
+        if (n[k] < 0 || (n[k] > 0 && (!src[k] || !dst[k])))
+            return fail(CGP_EINVAL, "rsqrt_batch: buffer %d", k);
+    for (int base = 0; base < count; base += kScaleBatch) {
+        ScaleBatch b{};
+        long long most = 0;
+        const int m = count - base < kScaleBatch ? count - base : kScaleBatch;
+        for (int k = 0; k < m; ++k) {
+            b.src[k] = src[base + k];
+            b.dst[k] = dst[base + k];
+            b.n[k] = n[base + k];
+            if (b.n[k] > most) most = b.n[k];
+        }
+        if (most == 0) continue;
+        hipLaunchKernelGGL(rsqrt_batch_kernel, dim3(grid_for(most), m), dim3(kBlock), 0,
+                           as_stream(stream), b);
+        const int rc = check_launch("rsqrt_batch_kernel");
         if (rc != CGP_OK) return rc;
     }
     return CGP_OK;

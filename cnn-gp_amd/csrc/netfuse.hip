@@ -290,10 +290,11 @@ __device__ __forceinline__ T relu_of(T c, T v1, T v2, const PolyTab& tab) {
     else
         return relu_fast(c, v1, v2, tab);
 }
-// The fp64 closed form reads scaled x-side variance maps (relu_q_n: the host passes
-// v × cgp_net_xvar_scale() = v/16 from ABI 9, v/4 before, for f64 launches without
-// CGP_FLAG_EXACT_RELU) and, when the producing conv scaled its weight and bias by 1/4
-// (QIN), a quartered input.
+// The fp64 closed form (relu_q_n, f64 launches without CGP_FLAG_EXACT_RELU) reads the maps
+// cgp_net_var_form() names in place of plain variances: 1/sqrt(v/8) on both sides (the
+// one-root form, default), or v × cgp_net_xvar_scale() = v/16 on the x side and v on the y
+// side (CGP_RELU_ONE_ROOT=0); and, when the producing conv scaled its weight and bias by
+// 1/4 (QIN), a quartered input.  u1 / u2 below are those maps' pixels, whatever the form.
 template <typename T, bool EX>
 constexpr bool kQuarter = !EX && sizeof(T) == 8;
 
@@ -1706,6 +1707,8 @@ size_t cgp_net_op_size(void) { return sizeof(cgp_net_op); }
 size_t cgp_net_args_size(void) { return sizeof(cgp_net_args); }
 
 int cgp_net_supertile(void) { return kST; }
+// the maps this file's relu_q_n was compiled to read (CGP_RELU_ONE_ROOT)
+int cgp_net_var_form(void) { return kNetVarForm; }
 
 int cgp_net_units(int32_t pairs) { return net_units(pairs <= 0 ? 1 : pairs); }
 

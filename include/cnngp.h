@@ -60,6 +60,20 @@ int cgp_abi_version(void);
  * var2_x without CGP_FLAG_EXACT_RELU): 1/16 from ABI 9 (1/4 in ABI 6-8).  cgp_var_chain_*
  * writes its qstore copies with it; a host scaling maps itself uses this value. */
 double cgp_net_xvar_scale(void);
+/* Which variance maps cgp_net_f64's closed-form ReLU reads through var_x / var_y (and
+ * var2_x / var2_y) of its op records -- an addition to ABI 12 (no struct or existing entry
+ * point changed); a host asks instead of assuming:
+ *   CGP_VAR_FORM_SCALED  x side: v × cgp_net_xvar_scale(), y side: plain v (the two-root
+ *                        form: every library before this query, and builds with
+ *                        -DCGP_RELU_ONE_ROOT=0)
+ *   CGP_VAR_FORM_RSQRT   both sides: m = 1/sqrt(v/8) as cgp_rsqrt_batch_f64 writes it
+ *                        (+inf where v = 0, unclamped); the one-root form, DESIGN.md §4.1.
+ *                        One map set serves an image on either side.
+ * cgp_net_f32, and cgp_net_f64 with CGP_FLAG_EXACT_RELU, read plain v on both sides in
+ * either form; kdiag is always the plain final variance. */
+#define CGP_VAR_FORM_SCALED 0
+#define CGP_VAR_FORM_RSQRT 1
+int cgp_net_var_form(void);
 const char* cgp_last_error(void);
 /* sizeof of the argument structs, so an FFI can verify its mirror of the layout */
 size_t cgp_conv_args_size(void);
@@ -200,6 +214,15 @@ int cgp_axpby_f32(double alpha, const float* a, double beta, const float* b, flo
  */
 int cgp_scale_batch_f64(int32_t count, const double* const* src, double* const* dst,
                         const int64_t* n, double alpha, void* stream);
+/*
+ * dst[k] = 1/sqrt(src[k]/8) (n[k] elements) for count buffers, in one launch per 32: the
+ * maps cgp_net_f64's closed-form ReLU reads when cgp_net_var_form() is CGP_VAR_FORM_RSQRT
+ * (an addition to ABI 12).  src holds plain variance maps; a zero variance gives +inf.  The
+ * division and the square root are correctly rounded, so every producer of these maps
+ * agrees bit for bit.  Every argument is checked before the first launch (CGP_EINVAL).
+ */
+int cgp_rsqrt_batch_f64(int32_t count, const double* const* src, double* const* dst,
+                        const int64_t* n, void* stream);
 
 /* load_kern's float32 → float64 widening, classify_gp.py:45-48 */
 int cgp_cast_f32_f64(const float* in, double* out, int64_t n, void* stream);
@@ -365,7 +388,10 @@ typedef struct cgp_net_op {
     const void* var_x;     /* ReLU input variances of the x images, [n1][h·w]; for
                               cgp_net_f64 without CGP_FLAG_EXACT_RELU: SCALED by
                               cgp_net_xvar_scale() (v/16 from ABI 9, v/4 before; the
-                              scaled closed form; var2_x likewise) */
+                              scaled closed form; var2_x likewise) when
+                              cgp_net_var_form() is CGP_VAR_FORM_SCALED; with
+                              CGP_VAR_FORM_RSQRT all four fields point at 1/sqrt(v/8)
+                              maps (cgp_rsqrt_batch_f64) instead of variances */
     const void* var_y;     /* ... of the y images, [n2][h·w] */
     const void* var2_x;    /* dst2's ReLU: variances of the result, [n1][h·w] */
     const void* var2_y;    /* [n2][h·w] */

@@ -2,7 +2,7 @@
 # A/B of one library variant (cnn-gp_amd/lib/ab/lib_$V.so, tools/build_variant.sh) against
 # the shipped library: the variant's whole-network parity tests first, then
 # tools/netbench.py (one B = 1024 Kxz tile per config) on uniform and MNIST-like images,
-# two rounds, alternating.
+# REPS rounds (default two), alternating.
 #   V=tol2 O=gpurun_out/x bash tools/ab_variant.sh
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -21,7 +21,7 @@ if [ -z "${SKIP_TESTS:-}" ]; then      # SKIP_TESTS=1: timing probes with wrong 
     echo "$V tests rc=$rc: $(tail -n 1 "$O/${V}_tests.log")"
     [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 fi
-for data in rand mnist; do for rep in 1 2; do for v in cur $V; do
+for data in rand mnist; do for rep in $(seq 1 ${REPS:-2}); do for v in cur $V; do
     lib=$PWD/cnn-gp_amd/lib/libcnngp.so; [ $v = $V ] && lib=$VL
     timeout -k 10 200 env CNNGP_LIB=$lib python tools/netbench.py --configs $CFGS --data $data \
         ${NB_ARGS:-} > "$O/ab_${v}_${data}_$rep.log" 2>&1 || exit 1
