@@ -68,6 +68,16 @@ class ReluNtkArgs(ctypes.Structure):
     ]
 
 
+class ErfArgs(ctypes.Structure):
+    """Mirror of cgp_erf_args (include/cnngp.h)."""
+    _fields_ = [
+        ("xy", _vp), ("theta", _vp), ("out_xy", _vp), ("out_theta", _vp), ("addend", _vp),
+        ("xx", _vp), ("yy", _vp),
+        ("nmaps", _i64), ("n1", _i64), ("n2", _i64),
+        ("hw", _i32), ("same", _i32), ("diag", _i32), ("flags", _i32),
+    ]
+
+
 class NetOp(ctypes.Structure):
     """Mirror of cgp_net_op (include/cnngp.h)."""
     _fields_ = [
@@ -143,6 +153,11 @@ SIGNATURES = {
     "cgp_relu_ntk_args_size": (ctypes.c_size_t, []),
     "cgp_relu_ntk_f64": (_i32, [ctypes.POINTER(ReluNtkArgs), _vp]),
     "cgp_relu_ntk_f32": (_i32, [ctypes.POINTER(ReluNtkArgs), _vp]),
+    "cgp_erf_args_size": (ctypes.c_size_t, []),
+    "cgp_erf_f64": (_i32, [ctypes.POINTER(ErfArgs), _vp]),
+    "cgp_erf_f32": (_i32, [ctypes.POINTER(ErfArgs), _vp]),
+    "cgp_var_erf_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "cgp_var_erf_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "cgp_var_relu_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "cgp_var_relu_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
@@ -213,6 +228,7 @@ def load():
         if lib.cgp_conv_args_size() != ctypes.sizeof(ConvArgs) or \
                 lib.cgp_relu_args_size() != ctypes.sizeof(ReluArgs) or \
                 lib.cgp_relu_ntk_args_size() != ctypes.sizeof(ReluNtkArgs) or \
+                lib.cgp_erf_args_size() != ctypes.sizeof(ErfArgs) or \
                 lib.cgp_net_op_size() != ctypes.sizeof(NetOp) or \
                 lib.cgp_net_args_size() != ctypes.sizeof(NetArgs) or \
                 lib.cgp_var_op_size() != ctypes.sizeof(VarOp) or \

@@ -22,7 +22,8 @@ from .program import Plan
 # (CGP_VAR_CHAIN=0: the layer-by-layer variance pipeline, one launch per op)
 VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
 
-__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Sequential", "Mixture", "Sum", "resnet_block")
+__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "Sequential", "Mixture", "Sum",
+           "resnet_block")
 
 
 def _stream_handle(device):
@@ -180,7 +181,8 @@ class NNGPKernel(nn.Module):
     def set_exact_relu(self, enabled: bool):
         """Evaluate the ReLU map op by op exactly like the reference (correctly rounded
         1/sqrt, sqrt, acos, division) instead of the closed form (default; within 1e-14 of
-        the exact map, see csrc/relu_poly.h).  For parity studies; ~2x slower."""
+        the exact map, see csrc/relu_poly.h).  For parity studies; ~2x slower.  An Erf has
+        one evaluation mode and ignores it."""
         for m in self.modules():
             m.__dict__["_cgp_exact_relu"] = bool(enabled)
         return self
@@ -250,9 +252,13 @@ class NNGPKernel(nn.Module):
                             θ = acos(clamp(c·rsqrt(v₁v₂ + f32_tiny), -1, 1)) of the
                             reference's ReLU (kernels.py:146-151); Θ' = Θ/2 exactly where
                             the reference overrides K' (same and i = j, or same and diag)
+            Erf             K' = (2/π)·atan(2c/√D),  Θ' = Θ·κ̇,  κ̇ = (4/π)/√D with
+                            D = 1 + 2(v₁ + v₂) + 4(v₁v₂ − c²), raised to 1 below 1;
+                            κ̇ = (4/π)/√(1 + 4v) where K' is overridden  
             Sum / Mixture   the same (weighted) sum on both
 
-        and the result is Θ of the final 1x1 value; a model without a Conv2d gives zeros.
+        and the result is Θ of the final 1x1 value; a model without a Conv2d gives zeros
+        (and K from forward itself).
         Equivalently Θ = Σ over all Conv2d outputs of ⟨∂K_final/∂K_xy^l, K_xy^l⟩ at fixed
         variances.  Always evaluated layer by layer (program.ntk_steps: the whole-network
         kernel carries one map); honours set_exact_relu."""
@@ -276,6 +282,12 @@ class NNGPKernel(nn.Module):
         if plan.final_hw != (1, 1):                              # kernels.py:53-57
             raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
                                " per pair, not 1x1: add a final Conv2d covering the map")
+        if not any(o.kind == "conv" for o in plan.prog.ops):
+            # no Conv2d, no parameters: Θ = 0 and there is no second stream to carry, so K
+            # is forward's own run, bit for bit whichever path forward takes (the
+            # whole-network kernel's fp64 ReLU and cgp_relu_* differ by an ulp on some pixels)
+            k = self._run(x, y, same, diag, stream)
+            return k, torch.zeros_like(k)
         sfx = Plan._sfx(x.dtype)
         lib = N.load()
         # per-image variances of the inputs (kernels.py:48-49), then of every ReLU's source
@@ -486,6 +498,16 @@ class Conv2d(NNGPKernel):
 class ReLU(NNGPKernel):
     """kernels.py:128-165 — the arc-cosine covariance map (device: relu_cov)."""
     f32_tiny = np.finfo(np.float32).tiny
+
+    def layers(self):
+        return 0
+
+
+class Erf(NNGPKernel):
+    """The erf nonlinearity (no reference counterpart; the paper's second closed form,
+    Williams 1997): K' = (2/π)·asin(2c/√((1+2v₁)(1+2v₂))), evaluated in the atan form of
+    DESIGN §3.2 (device: erf_pair).  Runs on the layer path; set_exact_relu has no effect
+    on it."""
 
     def layers(self):
         return 0

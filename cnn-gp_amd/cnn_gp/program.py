@@ -7,17 +7,19 @@ whole [N1·N2, 1, H, W] covariance tensor.  Here the tree is flattened once into
     v0 = moments(x, y)               kernels.py:44-49
     v  = conv(u, geometry)           kernels.py:92-98
     v  = relu(u)                     kernels.py:134-165
+    v  = erf(u)                      Erf (no reference counterpart)
     v  = add[(coef, u), ...]         Sum (kernels.py:252-254) / Mixture (:220-225)
 
 and then split into two device pipelines:
 
 * the VARIANCE pipeline runs every op, unfused, on the per-image maps [xx | yy]
   ((N1 + N2) maps — negligible next to the N1·N2 pair maps) and keeps the variances
-  of every value a ReLU consumes;
+  of every value a ReLU or Erf consumes;
 * the PAIR pipeline runs on the N1·N2 maps with ops fused so each HBM pass does the
   most work:  [ReLU|moments] → Conv → [ReLU] → [+ addend]  is ONE kernel
   (cgp_conv_*), a ReLU not adjacent to a single-use conv is cgp_relu_* (+ addend),
-  and only sums that cannot be folded into their producer run as cgp_axpby_*.
+  an Erf is always its own pass cgp_erf_* (+ addend), and only sums that cannot be
+  folded into their producer run as cgp_axpby_*.
 
 Fusion changes no arithmetic: each fused stage performs exactly the operations of the
 op it replaces (a + b == b + a in IEEE, so folding a Sum into either branch is exact).
@@ -48,7 +50,7 @@ class ConvGeom:
 
 @dataclasses.dataclass
 class Op:
-    kind: str                              # 'conv' | 'relu' | 'add' | 'moments'
+    kind: str                              # 'conv' | 'relu' | 'erf' | 'add' | 'moments'
     dst: int
     src: Optional[int] = None
     geom: Optional[ConvGeom] = None
@@ -128,6 +130,11 @@ def _emit(prog: Program, mod, v: int) -> int:
         prog.ops.append(Op("relu", out, src=v, shape_in=prog.shapes[v],
                            shape_out=prog.shapes[v]))
         return out
+    if isinstance(mod, K.Erf):
+        out = prog.new_value(prog.shapes[v])
+        prog.ops.append(Op("erf", out, src=v, shape_in=prog.shapes[v],
+                           shape_out=prog.shapes[v]))
+        return out
     if isinstance(mod, K.Sequential):
         for m in mod.mods:
             v = _emit(prog, m, v)
@@ -181,7 +188,9 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
          fold_moments: bool = True) -> list:
     """Return the fused op list for the pair pipeline (prog.ops is left untouched).
     ``pre_relu`` / ``fold_moments`` enable rules 3 / 4 (the whole-network kernel keeps
-    standalone ReLU and moments ops: in LDS they cost no extra memory pass)."""
+    standalone ReLU and moments ops: in LDS they cost no extra memory pass).  An erf op is
+    never a conv's pre- or post-stage (rules 1 and 3 match ReLU only); rule 2 may give it an
+    addend."""
     ops = [dataclasses.replace(o, terms=list(o.terms)) for o in prog.ops]
     if not enable:
         return ops
@@ -217,7 +226,7 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
             (_, t0), (_, t1) = a.terms
             for cand, other in ((t1, t0), (t0, t1)):
                 pi = producer(ops, cand)
-                if pi is None or ops[pi].kind not in ("conv", "relu") or \
+                if pi is None or ops[pi].kind not in ("conv", "relu", "erf") or \
                         ops[pi].addend is not None or uses.get(cand, 0) != 1:
                     continue
                 oi = producer(ops, other)
@@ -264,7 +273,7 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
 def needed_variances(ops) -> set:
     need = set()
     for o in ops:
-        if o.kind == "relu":
+        if o.kind in ("relu", "erf"):
             need.add(o.src)
         if o.pre == N.CGP_PRE_RELU:
             need.add(o.pre_var)
@@ -285,6 +294,8 @@ class NtkStep:
                    replaces the geometry's: 0 on the Θ stream)
     fn "relu":     dst = relu(src), variances of value ``var``           cgp_relu_*
     fn "relu_ntk": dst, dst_theta = relu(src), theta·κ̇                   cgp_relu_ntk_*
+    fn "erf":      dst = erf(src), variances of value ``var``            cgp_erf_* (theta NULL)
+    fn "erf_ntk":  dst, dst_theta = erf(src), theta·κ̇                    cgp_erf_*
     fn "axpby":    dst = Σ coef·buffer over ``terms`` (coef None: 1)     cgp_axpby_*
     """
     fn: str
@@ -317,10 +328,12 @@ def ntk_steps(prog: Program, v0: int, vf: int):
         Conv2d          K' = A(K) + var_bias,  Θ' = A(Θ) + K'
         ReLU            K' = relu(K),          Θ' = Θ·κ̇,  κ̇ = (π - θ)/2π  (1/2 where the
                         reference overrides K': same and i = j, or same and diag)
+        Erf             K' = erf(K),           Θ' = Θ·κ̇,  κ̇ = (4/π)/√D  
         Sum / Mixture   the same (weighted) sum on both streams
 
     A zero Θ is carried as None and costs nothing: the first conv's Θ' IS its K' (the same
-    buffer), a ReLU on a value with Θ = 0 is the plain cgp_relu_*, sums skip zero terms
+    buffer), a ReLU / Erf on a value with Θ = 0 is the plain cgp_relu_* / forward-only
+    cgp_erf_*, sums skip zero terms
     (a sum whose only non-zero term has weight 1 passes that term's buffer on)."""
     steps = []
     theta = {v0: None}
@@ -334,12 +347,12 @@ def ntk_steps(prog: Program, v0: int, vf: int):
                 steps.append(NtkStep("conv", ("T", d), src=theta[op.src], op=op, bias=0.0,
                                      addend=("K", d)))
                 theta[d] = ("T", d)
-        elif op.kind == "relu":
+        elif op.kind in ("relu", "erf"):
             if theta[op.src] is None:
-                steps.append(NtkStep("relu", ("K", d), src=("K", op.src), op=op, var=op.src))
+                steps.append(NtkStep(op.kind, ("K", d), src=("K", op.src), op=op, var=op.src))
                 theta[d] = None
             else:
-                steps.append(NtkStep("relu_ntk", ("K", d), src=("K", op.src), op=op,
+                steps.append(NtkStep(op.kind + "_ntk", ("K", d), src=("K", op.src), op=op,
                                      var=op.src, theta=theta[op.src], dst_theta=("T", d)))
                 theta[d] = ("T", d)
         elif op.kind == "add":
@@ -415,7 +428,7 @@ class Plan:
 
     # -- variance pipeline --------------------------------------------------------------
     def run_variances(self, xx0, yy0, n1, n2, same, stream, need=None):
-        """Per-image variance maps of every value a ReLU reads (or of ``need``).
+        """Per-image variance maps of every value a ReLU or Erf reads (or of ``need``).
         xx0/yy0: [n, H, W]."""
         sfx = self._sfx(xx0.dtype)
         dev = xx0.device
@@ -447,10 +460,10 @@ class Plan:
                     a.weight, a.bias = g.weight, g.bias
                     N.check(getattr(N.load(), f"cgp_conv_{sfx}")(a, stream), "cgp_conv")
                 out = (buf[:n1], buf[n1:])
-            elif op.kind == "relu":
+            elif op.kind in ("relu", "erf"):
                 xin, yin = vals[op.src]
                 buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
-                N.call(f"cgp_var_relu_{sfx}", N.ptr(xin), N.ptr(yin), n1, n2, ho * wo,
+                N.call(f"cgp_var_{op.kind}_{sfx}", N.ptr(xin), N.ptr(yin), n1, n2, ho * wo,
                        int(same), N.ptr(buf[:n1]), N.ptr(buf[n1:]), stream)
                 out = (buf[:n1], buf[n1:])
             elif op.kind == "add":
@@ -486,12 +499,16 @@ class Plan:
     def _var_chain(self, need, quarter, dev):
         """cgp_var_op records of the variance program (cached per need/quarter/device):
         LDS slots by first fit over the values' live ranges, store offsets per image.
-        None when the program has an op the chain kernel lacks (a Sum of > 4 terms)."""
+        None when the program has an op the chain kernel lacks (a Sum of > 4 terms, an
+        Erf)."""
         key = (frozenset(need), frozenset(quarter), str(dev))
         cache = self.__dict__.setdefault("_var_chains", {})
         if key in cache:
             return cache[key]
         ops = self.prog.ops
+        if any(op.kind not in ("conv", "relu", "add") for op in ops):
+            cache[key] = None
+            return None
         shapes = self.prog.shapes
         last = self._last_use(ops, self.vf)
         free = []                                  # (start, size) free LDS ranges
@@ -680,6 +697,17 @@ class Plan:
                 r.flags = self.flags
                 fn = getattr(lib, f"cgp_relu_{sfx}")
                 launch = (lambda fn=fn, r=r: N.check(fn(r, stream), "cgp_relu"))
+            elif op.kind == "erf":
+                out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
+                vx, vy = var[op.src]
+                r = N.ErfArgs()
+                r.xy, r.out_xy = N.ptr(vals[op.src]), N.ptr(out)
+                r.addend = N.ptr(vals[op.addend]) if op.addend is not None else None
+                r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                r.nmaps, r.n1, r.n2 = nmaps, n1, n2
+                r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
+                fn = getattr(lib, f"cgp_erf_{sfx}")
+                launch = (lambda fn=fn, r=r: N.check(fn(r, stream), "cgp_erf"))
             elif op.kind == "add":
                 out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
                 n = nmaps * ho * wo
@@ -706,9 +734,9 @@ class Plan:
 
     # -- NTK: K and Θ through the unfused program ------------------------------------------
     def ntk_need_var(self) -> set:
-        """The values whose variance maps the NTK run reads: every ReLU's source in the
-        unfused program (run_variances(need=...))."""
-        return {o.src for o in self.prog.ops if o.kind == "relu"}
+        """The values whose variance maps the NTK run reads: every ReLU's and Erf's source
+        in the unfused program (run_variances(need=...))."""
+        return {o.src for o in self.prog.ops if o.kind in ("relu", "erf")}
 
     def run_pairs_ntk(self, xy0, var, n1, n2, same, diag, stream):
         """Runs ntk_steps on the pair maps; returns (K, Θ) of the final value as
@@ -717,8 +745,8 @@ class Plan:
         maps of ntk_need_var().
 
         Buffers are freed after their last reader, as in run_pairs.  Peak live pair maps:
-        4 on a Conv2d/ReLU chain (K, Θ and K', Θ' of a cgp_relu_ntk_* step; 3 at a conv's
-        Θ launch), plus 2 (K and Θ) for every Sum / Mixture branch result or skip value
+        4 on a Conv2d/ReLU chain (K, Θ and K', Θ' of a cgp_relu_ntk_* or cgp_erf_* step;
+        3 at a conv's Θ launch), plus 2 (K and Θ) for every Sum / Mixture branch result or skip value
         waiting for its sum -- 6 inside a residual block of the ResNets."""
         sfx = self._sfx(xy0.dtype)
         lib = N.load()
@@ -778,6 +806,18 @@ class Plan:
                 r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
                 r.flags = self.flags
                 N.check(getattr(lib, f"cgp_relu_ntk_{sfx}")(r, stream), "cgp_relu_ntk")
+            elif st.fn in ("erf", "erf_ntk"):
+                out = bufs[st.dst] = new(op)
+                vx, vy = var[st.var]
+                r = N.ErfArgs()
+                r.xy, r.out_xy = N.ptr(bufs[st.src]), N.ptr(out)
+                if st.fn == "erf_ntk":
+                    tout = bufs[st.dst_theta] = new(op)
+                    r.theta, r.out_theta = N.ptr(bufs[st.theta]), N.ptr(tout)
+                r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                r.nmaps, r.n1, r.n2 = nmaps, n1, n2
+                r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
+                N.check(getattr(lib, f"cgp_erf_{sfx}")(r, stream), "cgp_erf")
             elif st.fn == "axpby":
                 out = bufs[st.dst] = new(op)
                 n = nmaps * ho * wo

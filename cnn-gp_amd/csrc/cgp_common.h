@@ -589,6 +589,49 @@ __device__ __forceinline__ T relu_pair(T c, const T* __restrict__ xx, const T* _
     return exact ? relu_exact(c, v1, v2) : relu_fast(c, v1, v2);
 }
 
+// ----------------------------------------------------------------------------------
+// erf networks (include/cnngp.h): one function per stream, shared by every
+// caller.  One evaluation mode: correctly rounded division and square root, the device
+// library's atan; every op rounded in T.
+// ----------------------------------------------------------------------------------
+__device__ __forceinline__ double atan_t(double x) { return atan(x); }
+__device__ __forceinline__ float atan_t(float x) { return atanf(x); }
+
+template <typename T> struct KErf {
+    static constexpr T two_over_pi = T(0.63661977236758134308);
+    static constexpr T four_over_pi = T(1.27323954473516268615);
+};
+
+// per-image variance: v' = (2/pi) atan(2v / sqrt(1 + 4v)); kdot = (4/pi)/sqrt(1 + 4v), the
+// NTK factor of a pair the reference overrides with its own variance
+template <typename T>
+__device__ __forceinline__ T erf_var(T v, T& kdot) {
+    const T s = sqrt_t(T(1) + T(4) * v);
+    kdot = KErf<T>::four_over_pi / s;
+    return KErf<T>::two_over_pi * atan_t((T(2) * v) / s);
+}
+template <typename T>
+__device__ __forceinline__ T erf_var(T v) {
+    T kdot;
+    return erf_var(v, kdot);
+}
+
+// erf of pair map m at pixel px with the overrides of relu_pair; kdot = dK'/dc at fixed
+// variances (dead code where the caller drops it)
+template <typename T>
+__device__ __forceinline__ T erf_pair(T c, const T* __restrict__ xx, const T* __restrict__ yy,
+                                      unsigned i, unsigned j, int hw, int px, int same,
+                                      int diag, T& kdot) {
+    const T v1 = xx[(size_t)i * hw + px];
+    if (same && (diag || i == j)) return erf_var(v1, kdot);  // xy' = xx'
+    const T v2 = yy[(size_t)j * hw + px];
+    T d = T(1) + T(2) * (v1 + v2) + T(4) * (v1 * v2 - c * c);
+    d = d < T(1) ? T(1) : d;                                 // NaN kept
+    const T s = sqrt_t(d);
+    kdot = KErf<T>::four_over_pi / s;
+    return KErf<T>::two_over_pi * atan_t((T(2) * c) / s);
+}
+
 // pair index -> (i, j)
 __device__ __forceinline__ void pair_of(unsigned m, const FastDiv& n2, int diag, unsigned& i,
                                         unsigned& j) {

@@ -197,6 +197,53 @@ int cgp_var_relu_f32(const float* xx, const float* yy, int64_t n1, int64_t n2, i
                      int32_t same, float* xx_out, float* yy_out, void* stream);
 
 /*
+ * The erf nonlinearity (an addition to ABI 12: no struct or existing entry point changed;
+ * no reference counterpart, the reference ships ReLU only).  The layer kernel of erf in
+ * closed form (Williams 1997; the paper's second nonlinearity), in the conventions of the
+ * ReLU entry points above -- per pixel (xy, xx, yy) = (c, v1, v2), no rescaling:
+ *   pair map    D = 1 + 2(v1 + v2) + 4(v1·v2 - c²), raised to 1 where it falls below 1
+ *               (D = (1+2v1)(1+2v2) - 4c² >= 1 for a valid covariance);
+ *               out_xy = (2/π)·atan(2c/√D)     [= (2/π)·asin(2c/√((1+2v1)(1+2v2)))]
+ *   variances   v' = (2/π)·atan(2v/√(1 + 4v)), the pair map at c = v1 = v2 = v
+ *   NTK         out_theta = theta·κ̇,  κ̇ = (4/π)/√D = ∂out_xy/∂c at fixed variances
+ *                                                   = E[erf'(u1)·erf'(u2)]
+ * Where cgp_relu_* overrides its map (same && !diag: pairs i == j; same && diag: all),
+ * out_xy = v'[i], the same bits cgp_var_erf_* writes, and κ̇ = (4/π)/√(1 + 4v).  A zero
+ * variance needs no guard (c = v = 0: out_xy = 0, κ̇ = 4/π).  One evaluation mode: division
+ * and square root correctly rounded, atan from the device math library; flags is ignored
+ * (CGP_FLAG_EXACT_RELU has no effect).
+ *
+ * theta == NULL: the forward-only pass (one map read, one write; out_theta unused).  With
+ * theta, one pass writes both maps.  In-place (out_xy == xy, out_theta == theta) is
+ * allowed, and theta may be xy itself: every element is read before it is written, by one
+ * thread.  addend (optional) is added to out_xy only, as a separate rounding.  same or diag
+ * need n1 == n2; hw is at most 2048; nmaps < 2^31.
+ */
+typedef struct cgp_erf_args {
+    const void* xy;         /* [nmaps][hw] */
+    const void* theta;      /* [nmaps][hw] or NULL */
+    void* out_xy;           /* [nmaps][hw] */
+    void* out_theta;        /* [nmaps][hw] (unused when theta is NULL) */
+    const void* addend;     /* [nmaps][hw] or NULL */
+    const void* xx;         /* [n1][hw] variances at the erf input */
+    const void* yy;         /* [n2][hw] (may be NULL when same && diag) */
+    int64_t nmaps, n1, n2;
+    int32_t hw, same, diag, flags;
+} cgp_erf_args;
+size_t cgp_erf_args_size(void);
+int cgp_erf_f64(const cgp_erf_args* args, void* stream);
+int cgp_erf_f32(const cgp_erf_args* args, void* stream);
+
+/*
+ * erf on the per-image variances: xx' = (2/π)·atan(2·xx/√(1 + 4·xx));
+ * yy' = xx' if same else the same map of yy.  xx: [n1][hw], yy: [n2][hw].
+ */
+int cgp_var_erf_f64(const double* xx, const double* yy, int64_t n1, int64_t n2, int32_t hw,
+                    int32_t same, double* xx_out, double* yy_out, void* stream);
+int cgp_var_erf_f32(const float* xx, const float* yy, int64_t n1, int64_t n2, int32_t hw,
+                    int32_t same, float* xx_out, float* yy_out, void* stream);
+
+/*
  * out = alpha·a + beta·b (b may be NULL: out = alpha·a), n elements.  The unfused form
  * of Sum (alpha = beta = 1, kernel_patch.py:43-63) and Mixture (kernels.py:220-225).
  * Products and the sum are rounded separately (no FMA contraction), like torch.
