@@ -185,6 +185,8 @@ SIGNATURES = {
     "cgp_net_args_size": (ctypes.c_size_t, []),
     "cgp_net_occupancy": (_i32, [_i32, _i32, _i32, _i32]),
     "cgp_net_program": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32]),
+    "cgp_net_program_lean": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32,
+                                    ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
     "cgp_net_validate": (_i32, [_vp, _i32, _i32]),
     "cgp_net_static_lds": (_i32, []),
     "cgp_net_f64": (_i32, [ctypes.POINTER(NetArgs), _vp]),

@@ -204,6 +204,21 @@ constexpr PolyCoef poly_coef(bool quartered) {
 }
 static __constant__ PolyCoef kReluPolyTabD = poly_coef(false);
 static __constant__ PolyCoef kReluPolyTabDq = poly_coef(true);
+// CGP_RELU_LEAN=1 (default, round 8): a compiled program drops two operations of the one-root
+// form where its op list and the launch's weights prove them idle (relu_q_n NOCAP / HALF,
+// netfuse.hip ProgLean); 0 rebuilds the round-7 kernel exactly.  The lean forms exist in the
+// one-root form only.
+#ifndef CGP_RELU_LEAN
+#define CGP_RELU_LEAN 1
+#endif
+constexpr bool kReluLean = CGP_RELU_LEAN != 0 && CGP_RELU_ONE_ROOT != 0;
+// every coefficient of a quartered table times 1/2 (exact): the tables of the HALF form
+template <class C>
+constexpr C half_coef(C t) {
+    for (double& v : t.c) v *= 0.5;
+    return t;
+}
+static __constant__ PolyCoef kReluPolyTabDqH = half_coef(poly_coef(true));
 
 // Range-adaptive ReLU: lower-degree fits of P on x in [0, kReluAdaptX0/1/2] = [0, 1/8],
 // [0, 1/4], [0, 3/8], quartered like kReluPolyTabDq.  Default (CGP_RELU_TOL=1, round 5):
@@ -232,19 +247,24 @@ constexpr AdaptCoef<D> adapt_coef(const double (&p)[D + 1]) {
 static __constant__ AdaptCoef<kReluAdaptDeg0> kReluAdaptTab0 = adapt_coef<kReluAdaptDeg0>(kReluAdaptP0);
 static __constant__ AdaptCoef<kReluAdaptDeg1> kReluAdaptTab1 = adapt_coef<kReluAdaptDeg1>(kReluAdaptP1);
 static __constant__ AdaptCoef<kReluAdaptDeg2> kReluAdaptTab2 = adapt_coef<kReluAdaptDeg2>(kReluAdaptP2);
+static __constant__ AdaptCoef<kReluAdaptDeg0> kReluAdaptTab0H = half_coef(adapt_coef<kReluAdaptDeg0>(kReluAdaptP0));
+static __constant__ AdaptCoef<kReluAdaptDeg1> kReluAdaptTab1H = half_coef(adapt_coef<kReluAdaptDeg1>(kReluAdaptP1));
+static __constant__ AdaptCoef<kReluAdaptDeg2> kReluAdaptTab2H = half_coef(adapt_coef<kReluAdaptDeg2>(kReluAdaptP2));
 
 typedef const __attribute__((address_space(4))) double* ConstD;   // scalar-loadable
 struct PolyTab {
     ConstD d, dq;
     ConstD a0, a1, a2;
 };
+// HALF: the quartered tables (dq, a0..a2) are the half-scaled ones (relu_q_n HALF)
+template <bool HALF = false>
 __device__ __forceinline__ PolyTab poly_table() {
     ConstD p = (ConstD)kReluPolyTabD.c;
-    ConstD q = (ConstD)kReluPolyTabDq.c;
+    ConstD q = (ConstD)(HALF ? kReluPolyTabDqH.c : kReluPolyTabDq.c);
     asm volatile("" : "+s"(p), "+s"(q));
-    ConstD a0 = (ConstD)kReluAdaptTab0.c;
-    ConstD a1 = (ConstD)kReluAdaptTab1.c;
-    ConstD a2 = (ConstD)kReluAdaptTab2.c;
+    ConstD a0 = (ConstD)(HALF ? kReluAdaptTab0H.c : kReluAdaptTab0.c);
+    ConstD a1 = (ConstD)(HALF ? kReluAdaptTab1H.c : kReluAdaptTab1.c);
+    ConstD a2 = (ConstD)(HALF ? kReluAdaptTab2H.c : kReluAdaptTab2.c);
     asm volatile("" : "+s"(a0), "+s"(a1), "+s"(a2));
     return PolyTab{p, q, a0, a1, a2};
 }
@@ -368,10 +388,21 @@ __device__ __forceinline__ unsigned vote_hi_max(const double (&u)[R]) {
     for (int r = 1; r < R; ++r) m = m > vote_hi(u[r]) ? m : vote_hi(u[r]);
     return m;
 }
-template <int R, bool QIN, int AD = 0>
+// The lean forms (one-root form only; a compiled program picks them per ReLU site where its
+// op list and the launch's weights prove the dropped operation idle, netfuse.hip ProgLean):
+// NOCAP: Y = m1·m2 without the cap.  Both variances come from a conv with w >= 0 and
+//   b >= 2^-60 of non-negative variances, so v >= b, m <= sqrt(8/b) and Y <= (8/b)(1 + a few
+//   ulp) <= 2^63.1 < 2^66: the fmin would return its first argument.
+// HALF: the input is non-negative (c + |c| = 2c exactly) and `tab` holds the half-scaled
+//   tables (poly_table<true>): every Horner step and the last fma then compute exactly half
+//   of the default form's values (a scaling by 1/2 commutes with rounding: c >= b/4 >= 2^-62
+//   keeps everything far from underflow), so the result is out/2 bit for bit, with one add
+//   less.  The producer stores out/2 and the convs that read it take 2w (exact).
+template <int R, bool QIN, int AD = 0, bool NOCAP = false, bool HALF = false>
 __device__ __forceinline__ void relu_q_n(double (&c)[R], const double (&v1q)[R],
                                          const double (&v2)[R], const PolyTab& tab,
                                          unsigned long long seg = ~0ull) {
+    static_assert(CGP_RELU_ONE_ROOT || (!NOCAP && !HALF), "lean forms: one-root form only");
     double sx[R], u[R], p[R];   // u: x4
 #if CGP_RELU_ONE_ROOT
     // One root per pixel.  v1q, v2 hold m = 1/sqrt(v/8) of the two sides, so Y = m1·m2 =
@@ -384,7 +415,10 @@ __device__ __forceinline__ void relu_q_n(double (&c)[R], const double (&v1q)[R],
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if constexpr (!QIN) c[r] *= 0.25;
-        Y[r] = __builtin_fmin(v1q[r] * v2[r], kYMax);
+        if constexpr (NOCAP)
+            Y[r] = v1q[r] * v2[r];
+        else
+            Y[r] = __builtin_fmin(v1q[r] * v2[r], kYMax);
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -470,7 +504,12 @@ __device__ __forceinline__ void relu_q_n(double (&c)[R], const double (&v1q)[R],
         horner_q<R, kReluPolyDegD>(p, u, tab.dq);
     }
 #pragma unroll
-    for (int r = 0; r < R; ++r) c[r] = __builtin_fma(sx[r], p[r], c[r] + __builtin_fabs(c[r]));
+    for (int r = 0; r < R; ++r) {
+        if constexpr (HALF)
+            c[r] = __builtin_fma(sx[r], p[r], c[r]);
+        else
+            c[r] = __builtin_fma(sx[r], p[r], c[r] + __builtin_fabs(c[r]));
+    }
 }
 // fp32: pixels in pairs on the packed-fp32 VALU (v_pk_fma_f32 / v_pk_mul_f32 /
 // v_pk_add_f32 do two fp32 lanes per instruction at the rate of one).  Each element sees

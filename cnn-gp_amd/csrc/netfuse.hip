@@ -302,14 +302,17 @@ constexpr bool kQuarter = !EX && sizeof(T) == 8;
 // may take the range-adaptive polynomial, see relu_q_n).  The fp32 closed form keeps its
 // full polynomial: its adaptive form measured neutral (the fp32 kernel is bound by its
 // per-op latency chain, not by issue; profiles/r3/ab_r3f_relu_adapt_f32.log)
-template <bool EXACT, bool QIN, typename T, int R, int AD = 0>
+// NC / HF: the fp64 form's lean variants (relu_q_n NOCAP / HALF; HF needs the half-scaled
+// tables in `tab`), picked per ReLU site by a compiled program (ProgLean below)
+template <bool EXACT, bool QIN, typename T, int R, int AD = 0, bool NC = false, bool HF = false>
 __device__ __forceinline__ void relu_n(T (&v)[R], const T (&u1)[R], const T (&u2)[R],
                                        const PolyTab& tab, unsigned long long seg = ~0ull) {
+    static_assert(!(NC || HF) || (!EXACT && sizeof(T) == 8), "lean ReLU forms: fp64 closed form");
     if constexpr (EXACT) {
 #pragma unroll
         for (int k = 0; k < R; ++k) v[k] = relu_exact_inl(v[k], u1[k], u2[k]);
     } else if constexpr (sizeof(T) == 8) {
-        relu_q_n<R, QIN, AD>(v, u1, u2, tab, seg);
+        relu_q_n<R, QIN, AD, NC, HF>(v, u1, u2, tab, seg);
     } else {
         relu_fast_n<R>(v, u1, u2, tab);
     }
@@ -337,12 +340,14 @@ constexpr int res_index(int h, int w) {
 // relu(result) -> dst2 (the next block's ReLU branch input, saving a separate op).
 // An op has the ReLU or dst2, never both, so one set of prefetched variances (u1, u2)
 // serves either.
-template <typename T, bool EX, bool DU, int R, int AD = 0>
+// NC / HF: the lean forms of the op's own ReLU (an HF op has no dst2, so the half-scaled
+// tables in `tab` never reach the dst2 ReLU).
+template <typename T, bool EX, bool DU, int R, int AD = 0, bool NC = false, bool HF = false>
 __device__ __forceinline__ void net_out(T* __restrict__ lds, const cgp_net_op& op, T (&v)[R],
                                         const int (&at)[R], const bool (&ok)[R],
                                         const T (&u1)[R], const T (&u2)[R],
                                         const PolyTab& tab, unsigned long long seg = ~0ull) {
-    if (op.relu) relu_n<EX, kQuarter<T, EX>, T, R, AD>(v, u1, u2, tab, seg);
+    if (op.relu) relu_n<EX, kQuarter<T, EX>, T, R, AD, NC, HF>(v, u1, u2, tab, seg);
     if (op.add >= 0) {
 #pragma unroll
         for (int k = 0; k < R; ++k)
@@ -487,12 +492,15 @@ __device__ __forceinline__ unsigned long long vote_lanes(int it) {
 #define CGP_NET_RES_UNDEF 1
 #endif
 // PRE: weight and bias arrive already scaled (a compiled program's records, prog_recs)
-template <typename T, bool EX, bool DU, class G, bool PRE = false>
+// NC / HF: the op's ReLU runs cap-free / on a non-negative input with a halved output
+// (relu_q_n NOCAP / HALF; a compiled program's lean chain, ProgLean)
+template <typename T, bool EX, bool DU, class G, bool PRE = false, bool NC = false,
+          bool HF = false>
 __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& op,
                                          const NetP<T>& p, const Pairs& pr) {
     constexpr int NP = G::NP;
     const int tid = opaque_tid();
-    const PolyTab tab = poly_table();
+    const PolyTab tab = poly_table<HF>();
     // a conv feeding the fp64 closed-form ReLU produces c/4 (exact: w/4, b/4) for relu_q_n
     const T qs = !PRE && kQuarter<T, EX> && op.relu ? T(0.25) : T(1);
     const T w = T(op.weight) * qs, b = T(op.bias) * qs;
@@ -544,7 +552,7 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
                 u1[0] = vs0.ldx(0);
                 u2[0] = vs0.ldy(0);
             }
-            net_out<T, EX, DU, 1>(lds, op, v, at, ok, u1, u2, tab);
+            net_out<T, EX, DU, 1, 0, NC, HF>(lds, op, v, at, ok, u1, u2, tab);
         }
     } else if constexpr (G::REDUCE) {
         prio_alu<NP, G::HW>();
@@ -575,7 +583,7 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
                 u1[0] = vs.ldx(0);
                 u2[0] = vs.ldy(0);
             }
-            net_out<T, EX, DU, 1>(lds, op, v, at, ok, u1, u2, tab);
+            net_out<T, EX, DU, 1, 0, NC, HF>(lds, op, v, at, ok, u1, u2, tab);
         }
     } else if constexpr (G::POINT) {
         prio_alu<NP, G::HW>();
@@ -597,7 +605,7 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
             u2[k] = (vs.on && ok[k]) ? vs.ldy((unsigned)pc) : T(1);
             v[k] = fma_t(w, src[q * arena + (r * G::S) * wsi + c * G::S], b);
         }
-        net_out<T, EX, DU, KP, NP == 1 ? 1 : 0>(lds, op, v, at, ok, u1, u2, tab);
+        net_out<T, EX, DU, KP, NP == 1 ? 1 : 0, NC, HF>(lds, op, v, at, ok, u1, u2, tab);
     } else if constexpr (G::DIRECT) {
         // one pass: item (q, g3, c) sums its WIN3 x TAPS input window straight from the
         // source slot (row sums, then column sums: the separable path's order, so the
@@ -679,9 +687,9 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
                     at[k] = q * arena + (g3 * G::R3 + k) * wso + c;
                     ok[k] = true;
                 }
-                net_out<T, EX, DU, G::R3, kAdaptOf<NP>>(lds, op, res[kv], at, ok, u1[kv],
-                                                        u2[kv], tab,
-                                                        NP == 1 ? ~0ull : vote_lanes<G::NV, NP>(it));
+                net_out<T, EX, DU, G::R3, kAdaptOf<NP>, NC, HF>(
+                    lds, op, res[kv], at, ok, u1[kv], u2[kv], tab,
+                    NP == 1 ? ~0ull : vote_lanes<G::NV, NP>(it));
             }
         }
     } else {
@@ -777,14 +785,14 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
                     ok[k] = true;
                 }
                 if (to_sum) {
-                    if (op.relu) relu_n<EX, kQuarter<T, EX>, T, G::R3, 1>(v, u1[kv], u2[kv], tab);
+                    if (op.relu)
+                        relu_n<EX, kQuarter<T, EX>, T, G::R3, 1, NC, HF>(v, u1[kv], u2[kv], tab);
 #pragma unroll
                     for (int k = 0; k < G::R3; ++k) sacc += v[k];
                 } else {
-                    net_out<T, EX, DU, G::R3, kAdaptOf<NP>>(lds, op, v, at, ok, u1[kv], u2[kv],
-                                                            tab,
-                                                            NP == 1 ? ~0ull
-                                                                    : vote_lanes<G::NV, NP>(it));
+                    net_out<T, EX, DU, G::R3, kAdaptOf<NP>, NC, HF>(
+                        lds, op, v, at, ok, u1[kv], u2[kv], tab,
+                        NP == 1 ? ~0ull : vote_lanes<G::NV, NP>(it));
                 }
             }
         }
@@ -1189,12 +1197,203 @@ struct ProgGeo {
     static constexpr GeoRow g = kGeoTable[o.code & CGP_NET_CODE_GEOMETRY];
     using G = NG<g.h, g.w, g.ho, g.wo, g.taps, g.s, g.off, NP>;
 };
-template <typename T, bool DU, int NP, int PID, int K>
+// ---- the lean chain of a program (round 8) -------------------------------
+// Two operations of the one-root ReLU (relu_q_n) are idle at most conv+ReLU sites when every
+// CONV record of the launch passes lean_rec_ok: the cap of Y (NOCAP: both variances are at
+// least b) and the c + |c| of the output (HALF: the input is non-negative; the site stores
+// out/2 and the convs that read it take 2w).  prog_lean walks a program's ops once and keeps
+// two facts per slot — an LDS interval [lo, hi) written by one op:
+//   nonneg: written by a ReLU (conv epilogue, dst2 or standalone; plus a non-negative
+//           addend, if any) or by a conv of a non-negative slot (plus the same);
+//   halved: holds out/2.
+// Slots written by CGP_NET_LOAD, MOMENTS (signed images) or LINEAR (its coefficients are not
+// part of the predicate) have no facts.  A conv+ReLU stores halved only if it has no addend
+// and no dst2 and, until its interval is overwritten whole, every op that touches it is a
+// CONV reading it as `src` from its origin (never `add`, never RELU / LINEAR / STORE, no
+// partial overwrite).  A CGP_NET_CODE_SUM conv never stores its map: its one reader is the
+// FROM_SUM reduction that follows.  A halved map still live when the program ends can only
+// be read as the launch's final slot, which net_impl checks (lean_final_clash).
+// Standalone RELU ops and dst2 ReLUs keep the default form.
+__host__ __device__ inline bool lean_rec_ok(double w, double b) {
+    // finite 0 <= w <= 2^60, 2^-60 <= b <= 2^60 (every comparison is false on NaN)
+    return w >= 0.0 && w <= 0x1p60 && b >= 0x1p-60 && b <= 0x1p60;
+}
+constexpr int kMaxProgOps = 24;   // at most 32: ProgLean::dbl_mask
+struct LeanOp {
+    bool nocap = false, half = false, dbl = false;   // dbl: the conv's source is halved (2w)
+};
+struct ProgLean {
+    LeanOp op[kMaxProgOps] = {};
+    unsigned dbl_mask = 0;   // bit k: op[k].dbl
+    int capfree = 0, addfree = 0;
+    int nend = 0, end_lo[4] = {}, end_hi[4] = {};   // halved maps live at the program's end
+    bool bad = false;                                // an op list the walk does not cover
+};
+struct LeanFact {
+    int lo = 0, hi = 0;
+    bool nonneg = false, halved = false;
+};
+constexpr bool lean_overlap(int lo, int hi, int lo2, int hi2) { return lo < hi2 && lo2 < hi; }
+constexpr bool op_is_sum(const ProgOp& o) {
+    return o.kind == CGP_NET_CONV && (o.code & CGP_NET_CODE_SUM) != 0;
+}
+// the interval op o reads through src / add and writes through dst / dst2 (hi == lo: none)
+constexpr int op_src_hi(const ProgOp& o) {
+    if (o.kind == CGP_NET_CONV) return o.src + kGeoTable[o.code & CGP_NET_CODE_GEOMETRY].h * o.ws_in;
+    if (o.kind == CGP_NET_RELU || o.kind == CGP_NET_LINEAR || o.kind == CGP_NET_STORE)
+        return o.src + o.h * o.ws_in;
+    return o.src;
+}
+constexpr bool op_reads_add(const ProgOp& o) {
+    return (o.kind == CGP_NET_CONV || o.kind == CGP_NET_RELU) ? o.add >= 0
+                                                              : o.kind == CGP_NET_LINEAR;
+}
+constexpr bool op_writes_dst(const ProgOp& o) { return o.kind != CGP_NET_STORE; }
+constexpr int op_ext(const ProgOp& o) { return o.h * o.ws_out; }
+// may the conv+ReLU op k of [ops, ops + n) store out/2 at [lo, hi)?  (*end: live at the end)
+constexpr bool lean_can_halve(const ProgOp* ops, int n, int k, int lo, int hi, bool* end) {
+    *end = false;
+    for (int m = k + 1; m < n; ++m) {
+        const ProgOp& r = ops[m];
+        if (op_reads_add(r) && lean_overlap(lo, hi, r.add, r.add + op_ext(r))) return false;
+        if (lean_overlap(lo, hi, r.src, op_src_hi(r)) &&
+            !(r.kind == CGP_NET_CONV && r.src == lo && op_src_hi(r) <= hi))
+            return false;
+        if (op_is_sum(r)) continue;   // no store
+        if (op_writes_dst(r) && lean_overlap(lo, hi, r.dst, r.dst + op_ext(r))) {
+            if (r.dst <= lo && r.dst + op_ext(r) >= hi) return true;
+            return false;
+        }
+        if (r.dst2 >= 0 && lean_overlap(lo, hi, r.dst2, r.dst2 + op_ext(r))) {
+            if (r.dst2 <= lo && r.dst2 + op_ext(r) >= hi) return true;
+            return false;
+        }
+    }
+    if (op_is_sum(ops[k]))   // never stored: read by the FROM_SUM reduction alone
+        return k + 1 < n && ops[k + 1].kind == CGP_NET_CONV &&
+               (ops[k + 1].code & CGP_NET_CODE_FROM_SUM) != 0 && ops[k + 1].src == lo;
+    *end = true;
+    return true;
+}
+constexpr ProgLean prog_lean(int pid) {
+    ProgLean L{};
+    const ProgInfo I = kProgs[pid];
+    const ProgOp* ops = kProgOps + I.first;
+    if (I.nops > kMaxProgOps) {
+        L.bad = true;
+        return L;
+    }
+    // one-pair code without dual outputs only (one pair per workgroup, or the two-pair
+    // head's halves).  The 4- and 16-pair stages gain registers with a second chain; the
+    // dual-output heads (the ResNets') measured 0.3-1% slower on their default chain with a
+    // lean one beside it (profiles/r8/ab_r8a_heads.txt), and the reference ResNets, whose
+    // convs have no bias, never take it
+    if (I.pairs > 2 || I.dual) return L;
+    constexpr int kMaxFacts = 8;
+    LeanFact f[kMaxFacts] = {};
+    int nf = 0;
+    auto find = [&](int lo, int hi) -> const LeanFact* {   // the fact a read of [lo, hi) sees
+        for (int n = 0; n < nf; ++n)
+            if (f[n].lo == lo && hi <= f[n].hi) return &f[n];
+        return nullptr;
+    };
+    auto touches_halved = [&](int lo, int hi) {
+        for (int n = 0; n < nf; ++n)
+            if (f[n].halved && lean_overlap(lo, hi, f[n].lo, f[n].hi)) return true;
+        return false;
+    };
+    auto write = [&](int lo, int hi, bool nonneg, bool halved) {
+        int m = 0;
+        for (int n = 0; n < nf; ++n)
+            if (!lean_overlap(lo, hi, f[n].lo, f[n].hi)) f[m++] = f[n];
+        nf = m;
+        if (!nonneg) return;        // no facts: not kept
+        if (nf == kMaxFacts) {      // table full: forget the fact (halved ones must stay)
+            if (halved) L.bad = true;
+            return;
+        }
+        f[nf].lo = lo;
+        f[nf].hi = hi;
+        f[nf].nonneg = nonneg;
+        f[nf].halved = halved;
+        ++nf;
+    };
+    for (int k = 0; k < I.nops; ++k) {
+        const ProgOp& o = ops[k];
+        const int ext = op_ext(o);
+        const LeanFact* fs = find(o.src, op_src_hi(o));
+        const LeanFact* fa = op_reads_add(o) ? find(o.add, o.add + ext) : nullptr;
+        const bool add_nn = !op_reads_add(o) || (fa && fa->nonneg);
+        // a halved map is read by convs through src from its origin only (lean_can_halve)
+        if (op_reads_add(o) && touches_halved(o.add, o.add + ext)) L.bad = true;
+        if (o.kind != CGP_NET_CONV && op_src_hi(o) > o.src && touches_halved(o.src, op_src_hi(o)))
+            L.bad = true;
+        if (o.kind == CGP_NET_CONV) {
+            if (touches_halved(o.src, op_src_hi(o)) && !(fs && fs->halved)) L.bad = true;
+            const bool src_nn = fs && fs->nonneg;
+            L.op[k].dbl = fs && fs->halved;
+            if (L.op[k].dbl) L.dbl_mask |= 1u << k;
+            bool half = false;
+            if (o.relu) {
+                L.op[k].nocap = true;
+                ++L.capfree;
+                bool end = false;
+                half = src_nn && o.add < 0 && o.dst2 < 0 &&
+                       lean_can_halve(ops, I.nops, k, o.dst, o.dst + ext, &end);
+                if (half && end) {
+                    if (L.nend == 4) {
+                        half = false;
+                    } else {
+                        L.end_lo[L.nend] = o.dst;
+                        L.end_hi[L.nend++] = o.dst + ext;
+                    }
+                }
+                L.op[k].half = half;
+                L.addfree += half;
+            }
+            write(o.dst, o.dst + ext, (o.relu || src_nn) && add_nn, half);
+            if (o.dst2 >= 0) write(o.dst2, o.dst2 + ext, true, false);
+        } else if (o.kind == CGP_NET_RELU) {
+            write(o.dst, o.dst + ext, add_nn, false);
+        } else if (o.kind == CGP_NET_LINEAR) {
+            write(o.dst, o.dst + ext, false, false);
+            if (o.dst2 >= 0) write(o.dst2, o.dst2 + ext, true, false);
+        } else if (o.kind == CGP_NET_MOMENTS || o.kind == CGP_NET_LOAD) {
+            write(o.dst, o.dst + ext, false, false);
+        }
+    }
+    return L;
+}
+template <int PID>
+struct LeanOf {
+    static constexpr ProgLean L = prog_lean(PID < 0 ? 0 : PID);
+    static_assert(!L.bad, "prog_lean: a program the slot walk does not cover");
+};
+// the same walks for the host (cgp_net_program_lean, net_impl)
+#define CGP_LEAN_ROW(k) LeanOf<k>::L,
+constexpr ProgLean kLeanTab[] = {CGP_NET_PROGRAMS(CGP_LEAN_ROW)};
+#undef CGP_LEAN_ROW
+// would the launch's final slot read a map the lean chain of program pid leaves halved?
+bool lean_final_clash(int pid, int final_slot) {
+    const ProgLean& L = kLeanTab[pid];
+    for (int n = 0; n < L.nend; ++n)
+        if (final_slot >= L.end_lo[n] && final_slot < L.end_hi[n]) return true;
+    return false;
+}
+// a program kernel carries the lean chain beside the default one: fp64, with a site to gain
+template <typename T, int PID>
+constexpr bool kLeanProg = PID >= 0 && kReluLean && sizeof(T) == 8 &&
+                           LeanOf<PID>::L.capfree + LeanOf<PID>::L.addfree > 0;
+
+// LEAN: the lean chain (the workgroup found every CONV record lean_rec_ok; prog_recs then
+// holds 2w for the convs that read a halved map)
+template <typename T, bool DU, int NP, int PID, int K, bool LEAN = false>
 __device__ __forceinline__ void prog_ops(T* __restrict__ lds, const NetP<T>& p, const Pairs& pr,
                                          int tid, const ProgRec* recs) {
     constexpr ProgInfo I = kProgs[PID];
     if constexpr (K < I.nops) {
         constexpr ProgOp o = kProgOps[I.first + K];
+        constexpr LeanOp lean = LEAN ? LeanOf<PID>::L.op[K] : LeanOp{};
         const cgp_net_op op = prog_op<PID, K>(recs);
         if constexpr (o.zero_halo != 0) {
 #pragma unroll
@@ -1208,8 +1407,9 @@ __device__ __forceinline__ void prog_ops(T* __restrict__ lds, const NetP<T>& p, 
             }
         }
         if constexpr (o.kind == CGP_NET_CONV) {
-            net_conv<T, false, DU, typename ProgGeo<PID, K, NP>::G, kNetPrescale>(lds, op, p,
-                                                                                 pr);
+            static_assert(!lean.half || (o.relu && o.add < 0 && o.dst2 < 0), "halved output");
+            net_conv<T, false, DU, typename ProgGeo<PID, K, NP>::G, kNetPrescale, lean.nocap,
+                     lean.half>(lds, op, p, pr);
         } else if constexpr (o.kind == CGP_NET_RELU || o.kind == CGP_NET_LINEAR ||
                              o.kind == CGP_NET_MOMENTS) {
             net_elem<T, false, DU, o.kind, o.h, o.w, NP>(lds, op, p, pr);
@@ -1221,10 +1421,9 @@ __device__ __forceinline__ void prog_ops(T* __restrict__ lds, const NetP<T>& p, 
                 net_move<T, o.kind, NP>(lds, op, p, pr);
         }
         lds_barrier();
-        prog_ops<T, DU, NP, PID, K + 1>(lds, p, pr, tid, recs);
+        prog_ops<T, DU, NP, PID, K + 1, LEAN>(lds, p, pr, tid, recs);
     }
 }
-
 // the compiled program whose op list equals ops[0, nops) field by field (host memory), +1;
 // 0 if none
 int prog_match(const cgp_net_op* ops, int nops, int pairs, int dual, int lds_elems,
@@ -1268,18 +1467,33 @@ __global__ __launch_bounds__(kNTof<NP>) __attribute__((amdgpu_waves_per_eu(WPE))
     if (tid < UN * (kNT / 64)) red_part[tid] = T(0);
     __shared__ ProgRec prog_recs[kRecsOf<PID>];
     __shared__ long long next_u[2];
-    static_assert(sizeof(pair_tab) + sizeof(red_part) + sizeof(prog_recs) + sizeof(next_u) <=
-                      kStaticLds,
+    __shared__ int lean_flag;   // every CONV record of this launch is lean_rec_ok
+    static_assert(sizeof(pair_tab) + sizeof(red_part) + sizeof(prog_recs) + sizeof(next_u) +
+                      sizeof(lean_flag) <= kStaticLds,
                   "static LDS beyond the reserve the host checks count (kStaticLds)");
     if constexpr (PID >= 0) {
+        const ProgOp* po = kProgOps + kProgs[PID < 0 ? 0 : PID].first;
         for (int k = tid; k < kRecsOf<PID>; k += kNTof<NP>) {
             const cgp_net_op& r = p.ops[k];
             // a conv feeding the fp64 closed-form ReLU runs on w/4, b/4 (net_conv): scaled
             // here once per workgroup (exact) instead of per op and pair
-            const ProgOp& o = kProgOps[kProgs[PID < 0 ? 0 : PID].first + k];
+            const ProgOp& o = po[k];
             const double qs =
                 kNetPrescale && kQuarter<T, false> && o.kind == CGP_NET_CONV && o.relu ? 0.25 : 1.0;
-            prog_recs[k] = ProgRec{r.weight * qs, r.bias * qs, r.var_x, r.var_y, r.var2_x,
+            double ws = qs;
+            if constexpr (kLeanProg<T, PID>) {
+                // the lean chain's condition, from the records this launch runs on: each
+                // filling thread reads every CONV record's weight and bias (a few loads, once
+                // per workgroup), so the records it writes and the flag agree
+                bool ok = true;
+                for (int n = 0; n < kRecsOf<PID>; ++n)
+                    if (po[n].kind == CGP_NET_CONV)
+                        ok = ok && lean_rec_ok(p.ops[n].weight, p.ops[n].bias);
+                // a conv whose source holds out/2 takes 2w (exact: w <= 2^60)
+                if (ok && ((LeanOf<PID>::L.dbl_mask >> k) & 1u)) ws *= 2.0;
+                if (k == 0) lean_flag = ok;
+            }
+            prog_recs[k] = ProgRec{r.weight * ws, r.bias * qs, r.var_x, r.var_y, r.var2_x,
                                    r.var2_y};
         }
     }
@@ -1309,121 +1523,19 @@ __global__ __launch_bounds__(kNTof<NP>) __attribute__((amdgpu_waves_per_eu(WPE))
         adv ^= 1;
         return v;
     };
-    for (long long u = advance(); u < end; u = advance()) {
-        if (tid == 0) grab = atomicAdd(ctr, 1ull);
-        Pairs pr;
-        pr.tab = pair_tab;
-        pr.u0 = u;
-        pr.red = red_part;
-        if constexpr (NP == 2) {
-            // one-pair slices sharing the workgroup's barriers: waves 2q, 2q + 1 run unit
-            // u + q (the next j of the same image i), each on its own arena.  The pair is
-            // uniform per wave, so each slice runs the one-pair code (scalar variance-map
-            // bases)
-            // every wave decodes the group's units (scalar); the group is skipped only when
-            // none of them is evaluated, so all waves agree at every barrier
-            const int q = __builtin_amdgcn_readfirstlane(tid >> 7);
-            unsigned iq = 0, jq = 0;
-            bool vq = false, wq = false, any = false;
-#pragma unroll
-            for (int s = 0; s < UN; ++s) {
-                unsigned is = 0, js = 0;
-                const bool vs = u + s < end && unit_pair(p, u + s, is, js);
-                const bool ws = vs && !(p.same && js <= is);
-                any |= ws;
-                if (s == q) {
-                    iq = is;
-                    jq = js;
-                    vq = vs;
-                    wq = ws;
-                }
-            }
-            if (!any) {   // below the diagonal of a same tile (or outside): K[i, i] only
-                if (p.final_stage && p.same && (tid & (kNT - 1)) == 0 && vq && jq == iq)
-                    p.out[(long long)iq * p.ldo + iq] = p.kdiag[iq];
-                continue;
-            }
-            Pairs ph;
-            ph.tab = pair_tab;
-            ph.u0 = u + q;
-            ph.red = red_part + q * (kNT / 64);
-            // a slice without a pair computes on clamped indices and stores nothing
-            ph.i = __builtin_amdgcn_readfirstlane(vq ? iq : 0u);
-            ph.j = __builtin_amdgcn_readfirstlane(vq ? jq : 0u);
-            T* lh = lds + q * p.lds_elems;
-            const int ht = tid & (kNT - 1);
-            if constexpr (PID < 0) {
-                for (int k = 0; k < p.nops; ++k) {
-                    const cgp_net_op op = load_op(ops_c(p.ops) + k);
-                    net_op<T, EX, DU, 1>(lh, op, p, ph, ht);
-                    lds_barrier();
-                }
-            } else {
-                prog_ops<T, DU, 1, PID, 0>(lh, p, ph, ht, prog_recs);
-            }
-            if (p.final_stage && ht == 0 && vq) {
-                if (wq) {
-                    const T v = lh[p.final_slot];
-                    p.out[(long long)ph.i * p.ldo + ph.j] = v;
-                    if (p.same) p.out[(long long)ph.j * p.ldo + ph.i] = v;
-                } else if (ph.j == ph.i) {
-                    p.out[(long long)ph.i * p.ldo + ph.i] = p.kdiag[ph.i];
-                }
-            }
-        } else {
-            if constexpr (NP == 1) {
-                if (!unit_pair(p, u, pr.i, pr.j)) continue;
-                pr.i = __builtin_amdgcn_readfirstlane(pr.i);   // uniform: scalar map offsets
-                pr.j = __builtin_amdgcn_readfirstlane(pr.j);
-                if (p.same && pr.j <= pr.i) {
-                    if (p.final_stage && pr.j == pr.i && tid == 0)
-                        p.out[(long long)pr.i * p.ldo + pr.i] = p.kdiag[pr.i];
-                    continue;
-                }
-            } else {
-                // the group's pair table; pairs outside the tile are computed on clamped
-                // indices and never stored
-                if (tid < NP) {
-                    unsigned iq = 0, jq = 0;
-                    unit_pair(p, u + tid, iq, jq);
-                    pair_tab[tid] = iq < p.n1 ? iq : p.n1 - 1;
-                    pair_tab[kMaxNP + tid] = jq < p.n2 ? jq : p.n2 - 1;
-                }
-                pr.i = pr.j = 0;
-                lds_barrier();
-            }
-            if constexpr (PID < 0) {
-                for (int k = 0; k < p.nops; ++k) {
-                    const cgp_net_op op = load_op(ops_c(p.ops) + k);
-                    net_op<T, EX, DU, NP>(lds, op, p, pr, tid);
-                    lds_barrier();
-                }
-            } else {
-                prog_ops<T, DU, NP, PID, 0>(lds, p, pr, tid, prog_recs);
-            }
-            if (p.final_stage) {
-                if constexpr (NP == 1) {
-                    if (tid == 0) {
-                        const T v = lds[p.final_slot];
-                        p.out[(long long)pr.i * p.ldo + pr.j] = v;
-                        if (p.same) p.out[(long long)pr.j * p.ldo + pr.i] = v;
-                    }
-                } else if (tid < NP) {
-                    unsigned iq, jq;
-                    if (u + tid < end && unit_pair(p, u + tid, iq, jq)) {
-                        if (!p.same || jq > iq) {
-                            const T v = lds[tid * p.lds_elems + p.final_slot];
-                            p.out[(long long)iq * p.ldo + jq] = v;
-                            if (p.same) p.out[(long long)jq * p.ldo + iq] = v;
-                        } else if (jq == iq) {
-                            p.out[(long long)iq * p.ldo + iq] = p.kdiag[iq];
-                        }
-                    }
-                }
-            }
+    // the pair walk (net_walk.inc): the lean chain's when the workgroup found the launch's
+    // records lean, else the default one
+    if constexpr (kLeanProg<T, PID>) {
+        if (__builtin_amdgcn_readfirstlane(lean_flag) != 0) {
+#define CGP_WALK_LEAN true
+#include "net_walk.inc"
+#undef CGP_WALK_LEAN
+            return;
         }
-        lds_barrier();
     }
+#define CGP_WALK_LEAN false
+#include "net_walk.inc"
+#undef CGP_WALK_LEAN
 }
 
 // waves per SIMD the LDS footprint of a workgroup allows (`waves` waves per workgroup,
@@ -1682,6 +1794,12 @@ int net_impl(const cgp_net_args* a, void* stream) {
         if (I.nops != a->nops || I.pairs != np || I.dual != (du ? 1 : 0) ||
             I.lds_elems != a->lds_elems || !(I.sizes & (int)sizeof(T)))
             return fail(CGP_EINVAL, "net: program %d does not fit this op list", prog);
+        // the lean chain may leave a map halved when the program ends; NetPlan's final slot
+        // is the last op's output, never such a map
+        if (kReluLean && sizeof(T) == 8 && !p.exact && a->final_stage &&
+            lean_final_clash(prog - 1, a->final_slot))
+            return fail(CGP_EINVAL, "net: final slot %d of program %d is a map slot",
+                        (int)a->final_slot, prog);
     }
     return net_launch<T>(p, p.exact != 0, du, np, lds_bytes, prog, stream);
 }
@@ -1781,6 +1899,22 @@ int cgp_net_program(const cgp_net_op* ops, int32_t nops, int32_t pairs, int32_t 
     if (!ops || nops <= 0) return 0;
     return prog_match(ops, nops, pairs <= 0 ? 1 : pairs, (flags & CGP_FLAG_NET_DUAL) ? 1 : 0,
                       lds_elems, itemsize);
+}
+
+int cgp_net_program_lean(const cgp_net_op* ops, int32_t nops, int32_t pairs, int32_t flags,
+                         int32_t lds_elems, int32_t itemsize, int32_t* capfree,
+                         int32_t* addfree) {
+    if (!kReluLean || !ops || nops <= 0 || itemsize != 8 || (flags & CGP_FLAG_EXACT_RELU))
+        return 0;
+    const int k = prog_match(ops, nops, pairs <= 0 ? 1 : pairs,
+                             (flags & CGP_FLAG_NET_DUAL) ? 1 : 0, lds_elems, itemsize);
+    if (k <= 0) return 0;
+    for (int n = 0; n < nops; ++n)
+        if (ops[n].kind == CGP_NET_CONV && !lean_rec_ok(ops[n].weight, ops[n].bias)) return 0;
+    const ProgLean& L = kLeanTab[k - 1];
+    if (capfree) *capfree = L.capfree;
+    if (addfree) *addfree = L.addfree;
+    return 1;
 }
 
 int cgp_net_f64(const cgp_net_args* args, void* stream) { return net_impl<double>(args, stream); }

@@ -548,6 +548,21 @@ int cgp_net_units(int32_t pairs);
  * (net_programs.h); a program kernel runs them with every offset an immediate. */
 int cgp_net_program(const cgp_net_op* ops, int32_t nops, int32_t pairs, int32_t flags,
                     int32_t lds_elems, int32_t itemsize);
+/* An addition to ABI 12 (a query: nothing on the production path calls it).  A compiled fp64
+ * program holds a second, lean op chain beside the default one: conv+ReLU sites without the
+ * cap of the one-root form ("cap-free") and, on non-negative inputs, without its max(c, 0)
+ * add ("add-free": the site stores out/2 and its reader convs take 2w), bit-identical to
+ * the default chain.  Every workgroup picks the lean chain by itself
+ * when each CGP_NET_CONV record of the launch has a finite weight 0 <= w <= 2^60 and a bias
+ * 2^-60 <= b <= 2^60.  Returns 1 and writes the number of ReLU sites of the program that
+ * then run cap-free and add-free when ops[0, nops) (HOST memory) matches a program
+ * (cgp_net_program's arguments) whose kernel would take the lean chain on these records;
+ * 0 when no program matches, a record fails that condition, itemsize is not 8, flags has
+ * CGP_FLAG_EXACT_RELU, or the library was built with CGP_RELU_LEAN=0 or
+ * CGP_RELU_ONE_ROOT=0.  capfree / addfree may be NULL. */
+int cgp_net_program_lean(const cgp_net_op* ops, int32_t nops, int32_t pairs, int32_t flags,
+                         int32_t lds_elems, int32_t itemsize, int32_t* capfree,
+                         int32_t* addfree);
 /* ABI 10: CGP_OK, or CGP_EINVAL (message in cgp_last_error) when the op list (HOST memory)
  * breaks the CGP_NET_CODE_SUM / CGP_NET_CODE_FROM_SUM preconditions for `pairs` pairs per
  * workgroup.  cnn_gp.netplan calls it once per stage before the first launch. */
