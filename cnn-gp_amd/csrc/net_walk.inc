@@ -3,7 +3,7 @@
 // program (kLeanProg) holds two walks behind one workgroup-uniform branch, so neither walk
 // carries the other's registers; every other kernel holds this loop once, as before.
 // Uses the kernel's locals: p, lds, tid, beg, end, advance, grab, ctr, pair_tab, red_part,
-// prog_recs and its template parameters.
+// prog_recs, hx and its template parameters.
     for (long long u = advance(); u < end; u = advance()) {
         if (tid == 0) grab = atomicAdd(ctr, 1ull);
         Pairs pr;
@@ -54,7 +54,7 @@
                     lds_barrier();
                 }
             } else {
-                prog_ops<T, DU, 1, PID, 0, CGP_WALK_LEAN>(lh, p, ph, ht, prog_recs);
+                prog_ops<T, DU, 1, PID, 0, CGP_WALK_LEAN>(lh, p, ph, ht, prog_recs, hx);
             }
             if (p.final_stage && ht == 0 && vq) {
                 if (wq) {
@@ -94,7 +94,7 @@
                     lds_barrier();
                 }
             } else {
-                prog_ops<T, DU, NP, PID, 0, CGP_WALK_LEAN>(lds, p, pr, tid, prog_recs);
+                prog_ops<T, DU, NP, PID, 0, CGP_WALK_LEAN>(lds, p, pr, tid, prog_recs, hx);
             }
             if (p.final_stage) {
                 if constexpr (NP == 1) {

@@ -392,6 +392,13 @@ struct VarSrc {
     __device__ __forceinline__ T ldy(unsigned px, int k = 0) const {
         return *(GP<T>)(y + (size_t)(yo + px * (unsigned)sizeof(T)) + k * (int)sizeof(T));
     }
+    // the same with the per-lane part in bytes (ConvHoist::px)
+    __device__ __forceinline__ T ldxb(unsigned pb, int k) const {
+        return *(GP<T>)(x + (size_t)(xo + pb) + k * (int)sizeof(T));
+    }
+    __device__ __forceinline__ T ldyb(unsigned pb, int k) const {
+        return *(GP<T>)(y + (size_t)(yo + pb) + k * (int)sizeof(T));
+    }
 };
 // UNI: i and j are the same in every lane (one pair per workgroup), so their offsets fold
 // into the scalar bases
@@ -491,14 +498,72 @@ __device__ __forceinline__ unsigned long long vote_lanes(int it) {
 #ifndef CGP_NET_RES_UNDEF
 #define CGP_NET_RES_UNDEF 1
 #endif
+// CGP_NET_HOIST=1 (default, round 9): a compiled one-pair fp64 program whose separable convs
+// all share one geometry and one pair of pitches (kHoistProg: the ConvNet's seven 7x7 convs,
+// the Residual net's nine 4x4 ones; the ResNets' 3x3 convs take the one-pass path)
+// decodes a thread's items once per kernel instead of once per op and pair.  The item of a
+// thread in the row pass and in the column pass, and so every address below, depends on the
+// thread, the geometry, the pitches and the launch's scratch offset only: the pointers carry
+// the workgroup half's arena and p.hs, the op's src / dst are immediates of the program and
+// land in the instruction offsets.  Five registers held across the walk against about 29
+// integer VALU instructions per op (opaque_tid() keeps the per-op decode of every other
+// kernel out of the pair loop's registers).  0: the per-op decode everywhere.
+#ifndef CGP_NET_HOIST
+#define CGP_NET_HOIST 1
+#endif
+template <typename T>
+using LP = __attribute__((address_space(3))) T*;   // an LDS address: one 32-bit register
+template <typename T>
+struct ConvHoist {
+    LP<T> row;         // row pass: the item's first window cell for an op with src == src0
+    LP<T> hrow;        // row pass: its first row-sum cell
+    LP<T> col;         // column pass: the item's first row-sum cell
+    LP<T> at;          // output 0 of the item for an op with dst == dst0
+    unsigned px;       // byte offset of output 0 in a variance map (item 0's for an idle thread)
+    bool row_on, col_on;   // the thread has an item in the pass
+    // the slots of the program's first separable conv (immediates): an op adds src - src0 /
+    // dst - dst0, zero where the convs share their slots, so the offsets of a window's cells
+    // stay within the reach of the paired LDS reads
+    int src0, dst0;
+};
+template <typename T, class G>
+__device__ __forceinline__ ConvHoist<T> conv_hoist(T* lds, const NetP<T>& p, int tid, int wsi,
+                                                   int wso, int src0, int dst0) {
+    static_assert(G::NP == 1 && G::KH == 1 && G::KV == 1 && !G::POINT && !G::REDUCE && !G::DIRECT,
+                  "hoisted decode: one item per thread and pass of a separable conv");
+    ConvHoist<T> h;
+    h.src0 = src0;
+    h.dst0 = dst0;
+    h.row_on = G::NH % G::NT == 0 || tid < G::NH;
+    h.col_on = G::NV % G::NT == 0 || tid < G::NV;
+    const LP<T> base = (LP<T>)lds;
+    const int qi = udiv(tid, G::NG2), g2 = tid - qi * G::NG2;
+    h.row = base + (src0 + (G::Q0 + qi + G::OFF) * wsi + g2 * G::R2 * G::S + G::OFF);
+    h.hrow = base + p.hs + ((G::Q0 + qi) * G::WO + g2 * G::R2);
+    const int g3 = udiv(tid, G::WO), c = tid - g3 * G::WO;
+    h.col = base + p.hs + (g3 * G::R3 * G::S * G::WO + c);
+    h.at = base + (dst0 + g3 * G::R3 * wso + c);
+    // each address as one opaque register: left visible, the compiler splits the slots'
+    // constants off again and keeps a register per pair of window cells instead
+    asm volatile("" : "+v"(h.row), "+v"(h.hrow), "+v"(h.col), "+v"(h.at));
+    const int itc = h.col_on ? tid : 0;
+    const int g3c = udiv(itc, G::WO), cc = itc - g3c * G::WO;
+    h.px = (unsigned)(g3c * G::R3 * G::WO + cc) * (unsigned)sizeof(T);
+    return h;
+}
 // PRE: weight and bias arrive already scaled (a compiled program's records, prog_recs)
 // NC / HF: the op's ReLU runs cap-free / on a non-negative input with a halved output
 // (relu_q_n NOCAP / HALF; a compiled program's lean chain, ProgLean)
+// HO: the separable path takes its item decode from hx (ConvHoist)
 template <typename T, bool EX, bool DU, class G, bool PRE = false, bool NC = false,
-          bool HF = false>
+          bool HF = false, bool HO = false>
 __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& op,
-                                         const NetP<T>& p, const Pairs& pr) {
+                                         const NetP<T>& p, const Pairs& pr,
+                                         const ConvHoist<T>* hx = nullptr) {
     constexpr int NP = G::NP;
+    static_assert(!HO || (NP == 1 && !G::POINT && !G::REDUCE && !G::DIRECT && G::KH == 1 &&
+                          G::KV == 1),
+                  "hoisted decode: separable one-pair convs");
     const int tid = opaque_tid();
     const PolyTab tab = poly_table<HF>();
     // a conv feeding the fp64 closed-form ReLU produces c/4 (exact: w/4, b/4) for relu_q_n
@@ -697,7 +762,23 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
         constexpr int NHT = NP * G::NH, NVT = NP * G::NV, NZT = NP * G::NZ;
         // variances of this thread's outputs, in flight during the row pass
         T u1[G::KV][G::R3], u2[G::KV][G::R3];
-        if (vs0.on) {
+        if constexpr (HO) {
+            if (vs0.on) {
+                // through an opaque move: the offset's zero extension then stays in this block,
+                // where it folds into the loads' SGPR-base form (hoisted with the offset, it
+                // costs a register pair and a 64-bit VALU add per side and op)
+                unsigned pb = hx->px;
+                asm volatile("" : "+v"(pb));
+#pragma unroll
+                for (int k = 0; k < G::R3; ++k) {
+                    u1[0][k] = vs0.ldxb(pb, k * G::WO);
+                    u2[0][k] = vs0.ldyb(pb, k * G::WO);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < G::R3; ++k) u1[0][k] = u2[0][k] = T(1);
+            }
+        } else if (vs0.on) {
 #pragma unroll
             for (int kv = 0; kv < G::KV; ++kv) {
                 const int it = tid + kv * G::NT;
@@ -719,22 +800,35 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
                 for (int k = 0; k < G::R3; ++k) u1[kv][k] = u2[kv][k] = T(1);
         }
         // row pass: hs[q][c] = Σ_t in[q + OFF][c·S + OFF + t]
-#pragma unroll
-        for (int kh = 0; kh < G::KH; ++kh) {
-            const int it = tid + kh * G::NT;
-            if (NHT % G::NT == 0 || it < NHT) {
-                const int q = NP == 1 ? 0 : udiv(it, G::NH), l = it - q * G::NH;
-                const int qi = udiv(l, G::NG2), g2 = l - qi * G::NG2;
-                const T* row = lds + (op.src + q * arena + (G::Q0 + qi + G::OFF) * wsi +
-                                      g2 * G::R2 * G::S + G::OFF);
+        if constexpr (HO) {
+            if (hx->row_on) {
+                const LP<T> row = hx->row + (op.src - hx->src0);
                 T win[G::WIN2];
 #pragma unroll
                 for (int t = 0; t < G::WIN2; ++t) win[t] = row[t];
                 T o[G::R2];
                 win_sums<T, G::TAPS, G::S, G::R2>(win, o);
-                T* h = hs + q * arena + (G::Q0 + qi) * G::WO + g2 * G::R2;
 #pragma unroll
-                for (int t = 0; t < G::R2; ++t) h[t] = o[t];
+                for (int t = 0; t < G::R2; ++t) hx->hrow[t] = o[t];
+            }
+        } else {
+#pragma unroll
+            for (int kh = 0; kh < G::KH; ++kh) {
+                const int it = tid + kh * G::NT;
+                if (NHT % G::NT == 0 || it < NHT) {
+                    const int q = NP == 1 ? 0 : udiv(it, G::NH), l = it - q * G::NH;
+                    const int qi = udiv(l, G::NG2), g2 = l - qi * G::NG2;
+                    const T* row = lds + (op.src + q * arena + (G::Q0 + qi + G::OFF) * wsi +
+                                          g2 * G::R2 * G::S + G::OFF);
+                    T win[G::WIN2];
+#pragma unroll
+                    for (int t = 0; t < G::WIN2; ++t) win[t] = row[t];
+                    T o[G::R2];
+                    win_sums<T, G::TAPS, G::S, G::R2>(win, o);
+                    T* h = hs + q * arena + (G::Q0 + qi) * G::WO + g2 * G::R2;
+#pragma unroll
+                    for (int t = 0; t < G::R2; ++t) h[t] = o[t];
+                }
             }
         }
         // hs rows outside the input are zero (the scratch is shared by every conv); skipped
@@ -761,10 +855,12 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
 #pragma unroll
         for (int kv = 0; kv < G::KV; ++kv) {
             const int it = tid + kv * G::NT;
-            if (NVT % G::NT == 0 || it < NVT) {
+            if (HO ? hx->col_on : (NVT % G::NT == 0 || it < NVT)) {
+                // (HO: q, g3 and c are dead; the item's cells come from hx)
                 const int q = NP == 1 ? 0 : udiv(it, G::NV), l = it - q * G::NV;
                 const int g3 = udiv(l, G::WO), c = l - g3 * G::WO;
-                const T* col = lds + (p.hs + q * arena + g3 * G::R3 * G::S * G::WO + c);
+                const T* col = HO ? (const T*)hx->col
+                                  : lds + (p.hs + q * arena + g3 * G::R3 * G::S * G::WO + c);
                 T win[G::WIN3];
 #pragma unroll
                 for (int t = 0; t < G::WIN3; ++t) win[t] = col[t * G::WO];
@@ -781,7 +877,7 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
 #pragma unroll
                 for (int k = 0; k < G::R3; ++k) {
                     v[k] = fma_t(w, o[k], b);
-                    at[k] = q * arena + (g3 * G::R3 + k) * wso + c;
+                    at[k] = HO ? k * wso - hx->dst0 : q * arena + (g3 * G::R3 + k) * wso + c;
                     ok[k] = true;
                 }
                 if (to_sum) {
@@ -791,7 +887,7 @@ __device__ __forceinline__ void net_conv(T* __restrict__ lds, const cgp_net_op& 
                     for (int k = 0; k < G::R3; ++k) sacc += v[k];
                 } else {
                     net_out<T, EX, DU, G::R3, kAdaptOf<NP>, NC, HF>(
-                        lds, op, v, at, ok, u1[kv], u2[kv], tab,
+                        HO ? (T*)hx->at : lds, op, v, at, ok, u1[kv], u2[kv], tab,
                         NP == 1 ? ~0ull : vote_lanes<G::NV, NP>(it));
                 }
             }
@@ -1385,11 +1481,43 @@ template <typename T, int PID>
 constexpr bool kLeanProg = PID >= 0 && kReluLean && sizeof(T) == 8 &&
                            LeanOf<PID>::L.capfree + LeanOf<PID>::L.addfree > 0;
 
+// ---- one item decode per walk (CGP_NET_HOIST, ConvHoist) -------------------------------
+// is op o a separable conv (row pass + column pass through the row-sum scratch)?
+constexpr bool op_separable(const ProgOp& o) {
+    if (o.kind != CGP_NET_CONV) return false;
+    const GeoRow& g = kGeoTable[o.code & CGP_NET_CODE_GEOMETRY];
+    const bool point = g.taps == 1 && g.off == 0;
+    const bool reduce = g.ho == 1 && g.wo == 1 && g.off == 0 && g.taps == g.h && g.taps == g.w;
+    return !point && !reduce && g.taps > 3;
+}
+// the first separable conv of program pid if every separable conv of it has that one's
+// geometry and pitches and the program runs one pair per workgroup (half), else -1
+constexpr int prog_hoist_op(int pid) {
+    const ProgInfo I = kProgs[pid];
+    if (I.pairs > 2) return -1;
+    int first = -1;
+    for (int k = 0; k < I.nops; ++k) {
+        const ProgOp& o = kProgOps[I.first + k];
+        if (!op_separable(o)) continue;
+        if (first < 0) first = k;
+        const ProgOp& f = kProgOps[I.first + first];
+        if ((o.code & CGP_NET_CODE_GEOMETRY) != (f.code & CGP_NET_CODE_GEOMETRY) ||
+            o.ws_in != f.ws_in || o.ws_out != f.ws_out)
+            return -1;
+    }
+    return first;
+}
+// fp64 closed-form program kernels only (fp32 is bound by latency, not by issue)
+template <typename T, int PID>
+constexpr bool kHoistProg = CGP_NET_HOIST != 0 && PID >= 0 && sizeof(T) == 8 &&
+                            prog_hoist_op(PID < 0 ? 0 : PID) >= 0;
+
 // LEAN: the lean chain (the workgroup found every CONV record lean_rec_ok; prog_recs then
 // holds 2w for the convs that read a halved map)
 template <typename T, bool DU, int NP, int PID, int K, bool LEAN = false>
 __device__ __forceinline__ void prog_ops(T* __restrict__ lds, const NetP<T>& p, const Pairs& pr,
-                                         int tid, const ProgRec* recs) {
+                                         int tid, const ProgRec* recs,
+                                         const ConvHoist<T>& hx) {
     constexpr ProgInfo I = kProgs[PID];
     if constexpr (K < I.nops) {
         constexpr ProgOp o = kProgOps[I.first + K];
@@ -1408,8 +1536,9 @@ __device__ __forceinline__ void prog_ops(T* __restrict__ lds, const NetP<T>& p, 
         }
         if constexpr (o.kind == CGP_NET_CONV) {
             static_assert(!lean.half || (o.relu && o.add < 0 && o.dst2 < 0), "halved output");
+            constexpr bool hoist = kHoistProg<T, PID> && op_separable(o);
             net_conv<T, false, DU, typename ProgGeo<PID, K, NP>::G, kNetPrescale, lean.nocap,
-                     lean.half>(lds, op, p, pr);
+                     lean.half, hoist>(lds, op, p, pr, &hx);
         } else if constexpr (o.kind == CGP_NET_RELU || o.kind == CGP_NET_LINEAR ||
                              o.kind == CGP_NET_MOMENTS) {
             net_elem<T, false, DU, o.kind, o.h, o.w, NP>(lds, op, p, pr);
@@ -1421,7 +1550,7 @@ __device__ __forceinline__ void prog_ops(T* __restrict__ lds, const NetP<T>& p, 
                 net_move<T, o.kind, NP>(lds, op, p, pr);
         }
         lds_barrier();
-        prog_ops<T, DU, NP, PID, K + 1, LEAN>(lds, p, pr, tid, recs);
+        prog_ops<T, DU, NP, PID, K + 1, LEAN>(lds, p, pr, tid, recs, hx);
     }
 }
 // the compiled program whose op list equals ops[0, nops) field by field (host memory), +1;
@@ -1523,6 +1652,19 @@ __global__ __launch_bounds__(kNTof<NP>) __attribute__((amdgpu_waves_per_eu(WPE))
         adv ^= 1;
         return v;
     };
+    // the item decode of the program's separable convs, once (ConvHoist): on the arena of this
+    // wave's half, as the walk hands it to the ops
+    ConvHoist<T> hx{};
+    if constexpr (kHoistProg<T, PID>) {
+        static_assert(NP <= 2, "hoisted decode: one-pair code");
+        constexpr int hk = prog_hoist_op(PID < 0 ? 0 : PID);
+        constexpr ProgOp ho = kProgOps[kProgs[PID < 0 ? 0 : PID].first + hk];
+        T* lh = lds;
+        if constexpr (NP == 2) lh += __builtin_amdgcn_readfirstlane(tid >> 7) * p.lds_elems;
+        hx = conv_hoist<T, typename ProgGeo<PID < 0 ? 0 : PID, hk, 1>::G>(lh, p, tid & (kNT - 1),
+                                                                        ho.ws_in, ho.ws_out, ho.src,
+                                                                        ho.dst);
+    }
     // the pair walk (net_walk.inc): the lean chain's when the workgroup found the launch's
     // records lean, else the default one
     if constexpr (kLeanProg<T, PID>) {
