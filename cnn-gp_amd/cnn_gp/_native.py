@@ -20,6 +20,7 @@ CGP_FLAG_GENERIC_CONV = 2
 CGP_FLAG_NET_DUAL = 4
 CGP_PRE_NONE, CGP_PRE_RELU, CGP_PRE_MOMENTS = 0, 1, 2
 CGP_POST_NONE, CGP_POST_RELU = 0, 1
+CGP_COV_NONE, CGP_COV_RELU, CGP_COV_ERF = 0, 1, 2
 CGP_NET_CONV, CGP_NET_RELU, CGP_NET_MOMENTS, CGP_NET_LINEAR = 0, 1, 2, 3
 CGP_NET_LOAD, CGP_NET_STORE = 4, 5
 CGP_NET_CODE_HS_CLEAN = 0x100
@@ -75,6 +76,30 @@ class ErfArgs(ctypes.Structure):
         ("xx", _vp), ("yy", _vp),
         ("nmaps", _i64), ("n1", _i64), ("n2", _i64),
         ("hw", _i32), ("same", _i32), ("diag", _i32), ("flags", _i32),
+    ]
+
+
+class CovConvArgs(ctypes.Structure):
+    """Mirror of cgp_cov_conv_args (include/cnngp.h)."""
+    _fields_ = [
+        ("in_", _vp), ("out", _vp), ("addend", _vp), ("xx", _vp), ("yy", _vp),
+        ("pair_i", _vp), ("pair_j", _vp),
+        ("npairs", _i64),
+        ("h", _i32), ("w", _i32), ("ho", _i32), ("wo", _i32),
+        ("taps", _i32), ("offset", _i32), ("stride", _i32), ("dilation", _i32),
+        ("post", _i32), ("same", _i32), ("flags", _i32), ("reserved", _i32),
+        ("weight", _f64), ("bias", _f64),
+    ]
+
+
+class CovNonlinArgs(ctypes.Structure):
+    """Mirror of cgp_cov_nonlin_args (include/cnngp.h)."""
+    _fields_ = [
+        ("in_", _vp), ("out", _vp), ("addend", _vp), ("xx", _vp), ("yy", _vp),
+        ("pair_i", _vp), ("pair_j", _vp),
+        ("npairs", _i64),
+        ("h", _i32), ("w", _i32), ("kind", _i32), ("same", _i32), ("flags", _i32),
+        ("reserved", _i32),
     ]
 
 
@@ -160,6 +185,16 @@ SIGNATURES = {
     "cgp_var_erf_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "cgp_var_relu_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "cgp_var_relu_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "cgp_cov_conv_args_size": (ctypes.c_size_t, []),
+    "cgp_cov_nonlin_args_size": (ctypes.c_size_t, []),
+    "cgp_cov_moments_f64": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "cgp_cov_moments_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "cgp_cov_conv_f64": (_i32, [ctypes.POINTER(CovConvArgs), _vp]),
+    "cgp_cov_conv_f32": (_i32, [ctypes.POINTER(CovConvArgs), _vp]),
+    "cgp_cov_nonlin_f64": (_i32, [ctypes.POINTER(CovNonlinArgs), _vp]),
+    "cgp_cov_nonlin_f32": (_i32, [ctypes.POINTER(CovNonlinArgs), _vp]),
+    "cgp_cov_pool_f64": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "cgp_cov_pool_f32": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_axpby_f32": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_scale_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _f64, _vp]),
@@ -231,6 +266,8 @@ def load():
                 lib.cgp_relu_args_size() != ctypes.sizeof(ReluArgs) or \
                 lib.cgp_relu_ntk_args_size() != ctypes.sizeof(ReluNtkArgs) or \
                 lib.cgp_erf_args_size() != ctypes.sizeof(ErfArgs) or \
+                lib.cgp_cov_conv_args_size() != ctypes.sizeof(CovConvArgs) or \
+                lib.cgp_cov_nonlin_args_size() != ctypes.sizeof(CovNonlinArgs) or \
                 lib.cgp_net_op_size() != ctypes.sizeof(NetOp) or \
                 lib.cgp_net_args_size() != ctypes.sizeof(NetArgs) or \
                 lib.cgp_var_op_size() != ctypes.sizeof(VarOp) or \

@@ -22,8 +22,8 @@ from .program import Plan
 # (CGP_VAR_CHAIN=0: the layer-by-layer variance pipeline, one launch per op)
 VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
 
-__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "Sequential", "Mixture", "Sum",
-           "resnet_block")
+__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "GlobalAvgPool", "Sequential", "Mixture",
+           "Sum", "resnet_block")
 
 
 def _stream_handle(device):
@@ -187,6 +187,15 @@ class NNGPKernel(nn.Module):
             m.__dict__["_cgp_exact_relu"] = bool(enabled)
         return self
 
+    def set_pool_workspace(self, max_bytes: Optional[int]):
+        """Bytes of device memory the position-pair maps of a model with a GlobalAvgPool
+        (and position_covariance) may take at once; the pairs of a tile run in chunks sized
+        to it, with bit-identical results.  None (default): a quarter of the device's free
+        memory, as image_variances takes."""
+        for m in self.modules():
+            m.__dict__["_cgp_pool_ws"] = None if max_bytes is None else int(max_bytes)
+        return self
+
     def _prologue(self, x, y, same, diag):
         """The argument rules of kernels.py:23-35, the dtype check and the empty-batch
         result shared by forward and ntk: (y, same, diag, empty) with ``empty`` the result
@@ -261,8 +270,12 @@ class NNGPKernel(nn.Module):
         (and K from forward itself).
         Equivalently Θ = Σ over all Conv2d outputs of ⟨∂K_final/∂K_xy^l, K_xy^l⟩ at fixed
         variances.  Always evaluated layer by layer (program.ntk_steps: the whole-network
-        kernel carries one map); honours set_exact_relu."""
+        kernel carries one map); honours set_exact_relu.  A model with a GlobalAvgPool
+        raises NotImplementedError (Θ on position-pair maps: DESIGN §8)."""
         y, same, diag, empty = self._prologue(x, y, same, diag)
+        if self._plan(x.size(2), x.size(3)).pool is not None:
+            from .program import POOL_RULE_NTK
+            raise NotImplementedError(POOL_RULE_NTK)
         if empty is not None:
             return (empty, empty.clone()) if return_nngp else empty
         out_device = x.device
@@ -316,6 +329,17 @@ class NNGPKernel(nn.Module):
         plan = self._plan(h, w)
         sfx = Plan._sfx(x.dtype)
         lib = N.load()
+        if plan.pool is not None:                                # GlobalAvgPool: DESIGN §3.3
+            r, pi, pj = self._run_pool(plan, plan.pool, x, y, same, diag, stream)
+            if diag:
+                return r.view(n1)
+            if not same:
+                return r.view(n1, n2)
+            # the pairs i <= j, mirrored: K is symmetric bit for bit
+            k = torch.empty((n1, n1), dtype=x.dtype, device=x.device)
+            k[pj, pi] = r.view(-1)
+            k[pi, pj] = r.view(-1)
+            return k
         if diag and same and VAR_CHAIN and self._net_plan(plan, x.element_size()) is not None:
             # same and diag: the reference overrides every K' with the image's own variance
             # (kernels.py:134-165), so the result IS the variance chain's final value — the
@@ -363,6 +387,66 @@ class NNGPKernel(nn.Module):
             raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
                                " per pair, not 1x1: add a final Conv2d covering the map")
         return out.view(n1) if diag else out.view(n1, n2)
+
+    # ---- GlobalAvgPool: position-pair maps ------------------------------------------
+    def _run_pool(self, plan, ps, x, y, same, diag, stream):
+        """Runs the launch list ``ps`` (program.pool_steps) on the pairs of a tile: all of
+        them, the pairs i <= j of a same tile, or (i, i) for diag.  Returns (the final value
+        of every pair [npairs, elements], pair_i, pair_j) with the pair lists as int64
+        index tensors."""
+        n1, c, h, w = x.shape
+        n2 = y.shape[0]
+        dev = x.device
+        if diag:
+            pi = pj = torch.arange(n1, device=dev)
+        elif same:
+            pi, pj = torch.triu_indices(n1, n1, device=dev)
+        else:
+            pi = torch.arange(n1, device=dev).repeat_interleave(n2)
+            pj = torch.arange(n2, device=dev).repeat(n1)
+        var = {}
+        if ps.need_var:
+            # per-image variances of the inputs (kernels.py:48-49), then of every value a
+            # nonlinearity reads: the layer path's own pipeline
+            var0 = torch.empty((n1 + n2, h, w), dtype=x.dtype, device=dev)
+            N.call(f"cgp_moments_var_{Plan._sfx(x.dtype)}", N.ptr(x), N.ptr(y), n1, n2, c,
+                   h * w, N.ptr(var0[:n1]), N.ptr(var0[n1:]), stream)
+            var = plan.run_variances(var0[:n1], var0[n1:], n1, n2, same, stream,
+                                     need=set(ps.need_var))
+        r = plan.run_pairs_pool(x, y, var, pi.to(torch.int32), pj.to(torch.int32), same, stream,
+                                ps, getattr(self, "_cgp_pool_ws", None))
+        return r, pi, pj
+
+    def position_covariance(self, x, y=None, same=None, diag=False):
+        """The position-pair covariance map of the model's output: S[i, j, p, q], the
+        covariance of pixel p of the output on x_i with pixel q of the output on y_j -- what
+        a GlobalAvgPool after this model averages.  [N1, N2, H', W', H', W'] (diag:
+        [N1, H', W', H', W']) in the order (p_row, p_col, q_row, q_col); its entries
+        [i, j, p, p] are the pair maps the layer path carries.  The model itself has no
+        GlobalAvgPool.  Arguments, dtypes and devices as forward; the maps of all pairs are
+        held at once on top of the workspace of set_pool_workspace."""
+        y, same, diag, empty = self._prologue(x, y, same, diag)
+        plan = self._plan(x.size(2), x.size(3))
+        ps = plan.body_steps()
+        ho, wo = ps.shapes[ps.final]
+        lead = (len(x),) if diag else (len(x), len(y))
+        if empty is not None:
+            return torch.empty(lead + (ho, wo, ho, wo), dtype=x.dtype, device=x.device)
+        out_device = x.device
+        dev = self._compute_device(x)
+        with torch.cuda.device(dev):
+            xd = _to_device(x, dev)
+            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
+            r, pi, pj = self._run_pool(plan, ps, xd, yd, same, diag, _stream_handle(dev))
+            # internal layout [p_row][q_row][p_col][q_col] -> (p_row, p_col, q_row, q_col)
+            r = r.view(-1, ho, ho, wo, wo).permute(0, 1, 3, 2, 4)
+            if same and not diag:
+                s = torch.empty(lead + (ho, wo, ho, wo), dtype=x.dtype, device=dev)
+                s[pj, pi] = r.permute(0, 3, 4, 1, 2)             # S_ji[q, p] = S_ij[p, q]
+                s[pi, pj] = r
+            else:
+                s = r.reshape(lead + (ho, wo, ho, wo))
+        return s.to(out_device) if out_device != dev else s
 
     # ---- Gram builds: every image's variance maps once per build -------------------
     # The reference (and forward above) recomputes the per-image variance recursion
@@ -508,6 +592,16 @@ class Erf(NNGPKernel):
     Williams 1997): K' = (2/π)·asin(2c/√((1+2v₁)(1+2v₂))), evaluated in the atan form of
     DESIGN §3.2 (device: erf_pair).  Runs on the layer path; set_exact_relu has no effect
     on it."""
+
+    def layers(self):
+        return 0
+
+
+class GlobalAvgPool(NNGPKernel):
+    """Global average pooling (no reference counterpart; the head of the CNN-GP and CNTK
+    papers' best networks): the 1x1 value mean over p, q of S[p, q], the covariance of pixel p
+    of x_i with pixel q of y_j.  Everything upstream of it runs on position-pair maps
+    (DESIGN §3.3); only Conv2d layers that keep the value 1x1 and Sum / Mixture may follow."""
 
     def layers(self):
         return 0

@@ -9,6 +9,8 @@ whole [N1·N2, 1, H, W] covariance tensor.  Here the tree is flattened once into
     v  = relu(u)                     kernels.py:134-165
     v  = erf(u)                      Erf (no reference counterpart)
     v  = add[(coef, u), ...]         Sum (kernels.py:252-254) / Mixture (:220-225)
+    v  = pool(u)                     GlobalAvgPool (no reference counterpart; DESIGN §3.3:
+                                     such a program runs on position-pair maps, pool_steps)
 
 and then split into two device pipelines:
 
@@ -50,7 +52,7 @@ class ConvGeom:
 
 @dataclasses.dataclass
 class Op:
-    kind: str                              # 'conv' | 'relu' | 'erf' | 'add' | 'moments'
+    kind: str                              # 'conv' | 'relu' | 'erf' | 'add' | 'pool' | 'moments'
     dst: int
     src: Optional[int] = None
     geom: Optional[ConvGeom] = None
@@ -134,6 +136,10 @@ def _emit(prog: Program, mod, v: int) -> int:
         out = prog.new_value(prog.shapes[v])
         prog.ops.append(Op("erf", out, src=v, shape_in=prog.shapes[v],
                            shape_out=prog.shapes[v]))
+        return out
+    if isinstance(mod, K.GlobalAvgPool):
+        out = prog.new_value((1, 1))
+        prog.ops.append(Op("pool", out, src=v, shape_in=prog.shapes[v], shape_out=(1, 1)))
         return out
     if isinstance(mod, K.Sequential):
         for m in mod.mods:
@@ -372,6 +378,133 @@ def ntk_steps(prog: Program, v0: int, vf: int):
 
 
 # ------------------------------------------------------------------------------------
+# global average pooling: the program on position-pair maps
+# ------------------------------------------------------------------------------------
+POOL_RULE_NONLIN = ("a ReLU or Erf downstream of a GlobalAvgPool is not implemented: it would "
+                    "need the pooled self-covariances of each image (DESIGN §8)")
+POOL_RULE_ONE = ("every path from the input to the output must pass through exactly one "
+                 "GlobalAvgPool in a model that contains one (DESIGN §8)")
+POOL_RULE_CONV = ("a Conv2d downstream of a GlobalAvgPool must keep the value 1x1 "
+                  "(e.g. Conv2d(1, var_weight=..., var_bias=...))")
+POOL_RULE_NTK = ("ntk: the neural tangent kernel of a model with a GlobalAvgPool is not "
+                 "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
+
+
+@dataclasses.dataclass
+class PoolStep:
+    """One launch of a pooled run.  Buffers are named by the SSA value they hold.
+
+    fn "moments": dst = mean_c x[c, p]·y[c, q]                          cgp_cov_moments_*
+    fn "conv":    dst = A(src)·weight + bias [→ ReLU, variances of value ``var``]
+                  [+ addend]                                             cgp_cov_conv_*
+    fn "nonlin":  dst = relu / erf (``post``) of src, variances of value ``var``
+                  [+ addend]                                             cgp_cov_nonlin_*
+    fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
+    fn "axpby":   dst = Σ coef·buffer over ``terms`` (coef None: 1)      cgp_axpby_*
+    ``free``: the buffers nothing reads after this launch."""
+    fn: str
+    dst: int
+    src: Optional[int] = None
+    op: Optional[Op] = None
+    post: int = N.CGP_COV_NONE
+    var: Optional[int] = None
+    addend: Optional[int] = None
+    terms: list = dataclasses.field(default_factory=list)
+    free: list = dataclasses.field(default_factory=list)
+
+    def reads(self):
+        r = [b for b in (self.src, self.addend) if b is not None]
+        return r + [b for _, b in self.terms]
+
+
+@dataclasses.dataclass
+class PoolSteps:
+    steps: list
+    shapes: dict        # buffer -> (h, w) of its value
+    maps: frozenset     # buffers that are position-pair maps: (h·w)² elements per pair
+    scalars: frozenset  # buffers downstream of the pool: one element per pair
+    pooled: frozenset   # every value of the unfused program at or after a pool
+    final: int
+    need_var: frozenset  # values whose per-image variance maps the nonlinearities read
+    peak: int           # elements per pair live at the fullest launch
+
+    def elems(self, b) -> int:
+        h, w = self.shapes[b]
+        return (h * w) ** 2 if b in self.maps else 1
+
+
+def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps:
+    """The launches of a program with a GlobalAvgPool, over the program fused with rules 1
+    and 2 (conv with a ReLU post-stage, a two-term Sum as an addend).  Values upstream of
+    the pool are position-pair maps S[p, q]; downstream they are 1x1 per pair, and only
+    linear ops may follow (they read no variances).  ``body``: the program has no pool and
+    its final value is a map (NNGPKernel.position_covariance).
+
+    Raises NotImplementedError naming the rule for a ReLU / Erf after a pool and for a path
+    that does not pass exactly one pool."""
+    pooled = {v0: False}
+    for op in prog.ops:
+        if op.kind in ("relu", "erf"):
+            if pooled[op.src]:
+                raise NotImplementedError(POOL_RULE_NONLIN)
+            pooled[op.dst] = False
+        elif op.kind == "pool":
+            if body:
+                raise ValueError("position_covariance: the model contains a GlobalAvgPool "
+                                 "(it is the map the pool would read: pass the body)")
+            if pooled[op.src]:
+                raise NotImplementedError(POOL_RULE_ONE)
+            pooled[op.dst] = True
+        elif op.kind == "conv":
+            if pooled[op.src] and tuple(op.shape_out) != (1, 1):
+                raise NotImplementedError(POOL_RULE_CONV)
+            pooled[op.dst] = pooled[op.src]
+        elif op.kind == "add":
+            sides = {pooled[t] for _, t in op.terms}
+            if len(sides) != 1:
+                raise NotImplementedError(POOL_RULE_ONE)
+            pooled[op.dst] = sides.pop()
+        else:
+            raise AssertionError(op.kind)
+    if not body and not pooled[vf]:
+        raise NotImplementedError(POOL_RULE_ONE)
+
+    steps = [PoolStep("moments", v0)]
+    for op in fuse(prog, v0, vf, True, pre_relu=False, fold_moments=False):
+        if op.kind == "conv":
+            relu = op.post == N.CGP_POST_RELU
+            steps.append(PoolStep("conv", op.dst, src=op.src, op=op,
+                                  post=N.CGP_COV_RELU if relu else N.CGP_COV_NONE,
+                                  var=op.post_var if relu else None, addend=op.addend))
+        elif op.kind in ("relu", "erf"):
+            steps.append(PoolStep("nonlin", op.dst, src=op.src, op=op,
+                                  post=N.CGP_COV_RELU if op.kind == "relu" else N.CGP_COV_ERF,
+                                  var=op.src, addend=op.addend))
+        elif op.kind == "pool":
+            steps.append(PoolStep("pool", op.dst, src=op.src, op=op))
+        else:
+            steps.append(PoolStep("axpby", op.dst, op=op, terms=list(op.terms)))
+    last = {}
+    for idx, st in enumerate(steps):
+        for b in st.reads():
+            last[b] = idx
+    last[vf] = len(steps)
+    bufs = [st.dst for st in steps]
+    ps = PoolSteps(steps, {b: prog.shapes[b] for b in bufs},
+                   frozenset(b for b in bufs if not pooled[b]),
+                   frozenset(b for b in bufs if pooled[b]),
+                   frozenset(v for v, p in pooled.items() if p), vf,
+                   frozenset(st.var for st in steps if st.var is not None), 0)
+    live = set()
+    for idx, st in enumerate(steps):
+        live.add(st.dst)
+        ps.peak = max(ps.peak, sum(ps.elems(b) for b in live))
+        st.free = sorted(b for b in live if last.get(b, -1) <= idx)
+        live.difference_update(st.free)
+    return ps
+
+
+# ------------------------------------------------------------------------------------
 # execution
 # ------------------------------------------------------------------------------------
 def _adjacent(x, y) -> bool:
@@ -405,6 +538,10 @@ class Plan:
         fh, fw = self.prog.shapes[self.vf]
         self.final_hw = (fh, fw)
         self.moments_fused = any(o.pre == N.CGP_PRE_MOMENTS for o in self.pair_ops)
+        # a model with a GlobalAvgPool runs on position-pair maps (run_pairs_pool); its
+        # rejections are raised here, when the program is compiled
+        self.pool = pool_steps(self.prog, self.v0, self.vf) \
+            if any(o.kind == "pool" for o in self.prog.ops) else None
 
     # -- helpers -----------------------------------------------------------------------
     @staticmethod
@@ -439,7 +576,10 @@ class Plan:
         keep = {}
         if self.v0 in need:
             keep[self.v0] = vals[self.v0]
+        pooled = self.pool.pooled if self.pool is not None else ()
         for idx, op in enumerate(ops):
+            if op.dst in pooled:
+                continue        # at or after a GlobalAvgPool: linear ops, no variances read
             ho, wo = op.shape_out
             if op.kind == "conv":
                 xin, yin = vals[op.src]
@@ -834,3 +974,100 @@ class Plan:
             for b in [b for b in bufs if last.get(b, -1) <= idx and b not in st.writes()]:
                 del bufs[b]
         return bufs[kbuf], (None if tbuf is None else bufs[tbuf])
+
+    # -- GlobalAvgPool: the program on position-pair maps ---------------------------------
+    def body_steps(self) -> PoolSteps:
+        """pool_steps of a model without a pool (position_covariance): the final value is
+        the position-pair map a GlobalAvgPool after the model would read."""
+        if "_body_steps" not in self.__dict__:
+            self._body_steps = pool_steps(self.prog, self.v0, self.vf, body=True)
+        return self._body_steps
+
+    def run_pairs_pool(self, x, y, var, pair_i, pair_j, same, stream, ps=None,
+                       max_bytes=None):
+        """Runs ``ps`` (default: the plan's own pool_steps) over the pairs (pair_i[m],
+        pair_j[m]) -- device int32 arrays -- in chunks of pairs; returns the final value of
+        every pair as [npairs, elements] (one element per pair after a pool).
+        x, y: images [n, C, H, W]; var: the variance maps of ps.need_var (run_variances).
+
+        A chunk takes ps.peak elements per pair at its fullest launch (every buffer is freed
+        after its last reader); chunks are sized to stay under ``max_bytes`` (default: a
+        quarter of the device's free memory).  Each kernel computes a pair from that pair's
+        data alone in a fixed order, so the result does not depend on the chunking."""
+        ps = self.pool if ps is None else ps
+        sfx = self._sfx(x.dtype)
+        lib = N.load()
+        dev = x.device
+        item = x.element_size()
+        npairs = pair_i.numel()
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        per_pair = ps.peak * item
+        chunk = int(max_bytes) // per_pair
+        if chunk < 1:
+            big = max(ps.elems(b) for b in ps.shapes)
+            raise RuntimeError(
+                f"GlobalAvgPool: one image pair needs {per_pair} bytes of position-pair maps "
+                f"({ps.peak} live elements of {item} bytes at the fullest launch; the largest "
+                f"map holds {big}), more than the workspace of {int(max_bytes)} bytes "
+                "(set_pool_workspace)")
+        # pairs·elements of one launch stay below 2^40 (the entry points count blocks in int32)
+        chunk = min(chunk, npairs, max(1, (1 << 40) // max(ps.elems(b) for b in ps.shapes)))
+        C = x.shape[1]
+        out = torch.empty((npairs, ps.elems(ps.final)), dtype=x.dtype, device=dev)
+        for a in range(0, npairs, chunk):
+            n = min(chunk, npairs - a)
+            pi, pj = pair_i[a:a + n], pair_j[a:a + n]
+            bufs = {}
+            for st in ps.steps:
+                h, w = ps.shapes[st.dst]
+                ne = ps.elems(st.dst)
+                dst = out[a:a + n] if st.dst == ps.final else \
+                    torch.empty((n, ne), dtype=x.dtype, device=dev)
+                bufs[st.dst] = dst
+                if st.fn == "moments":
+                    N.check(getattr(lib, f"cgp_cov_moments_{sfx}")(
+                        N.ptr(x), N.ptr(y), N.ptr(pi), N.ptr(pj), n, C, h, w, N.ptr(dst),
+                        stream), "cgp_cov_moments")
+                elif st.fn == "conv":
+                    g = st.op.geom
+                    r = N.CovConvArgs()
+                    r.in_, r.out = N.ptr(bufs[st.src]), N.ptr(dst)
+                    r.addend = N.ptr(bufs[st.addend]) if st.addend is not None else None
+                    if st.var is not None:
+                        vx, vy = var[st.var]
+                        r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
+                    (r.h, r.w), r.ho, r.wo = ps.shapes[st.src], h, w
+                    r.taps, r.offset, r.stride, r.dilation = g.taps, g.offset, g.stride, \
+                        g.dilation
+                    r.post, r.same, r.flags = st.post, int(same), self.flags
+                    r.weight, r.bias = g.weight, g.bias
+                    N.check(getattr(lib, f"cgp_cov_conv_{sfx}")(r, stream), "cgp_cov_conv")
+                elif st.fn == "nonlin":
+                    vx, vy = var[st.var]
+                    r = N.CovNonlinArgs()
+                    r.in_, r.out = N.ptr(bufs[st.src]), N.ptr(dst)
+                    r.addend = N.ptr(bufs[st.addend]) if st.addend is not None else None
+                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
+                    r.h, r.w, r.kind, r.same, r.flags = h, w, st.post, int(same), self.flags
+                    N.check(getattr(lib, f"cgp_cov_nonlin_{sfx}")(r, stream), "cgp_cov_nonlin")
+                elif st.fn == "pool":
+                    N.check(getattr(lib, f"cgp_cov_pool_{sfx}")(
+                        N.ptr(bufs[st.src]), n, ps.elems(st.src), N.ptr(dst), stream),
+                        "cgp_cov_pool")
+                elif st.fn == "axpby":
+                    for k, (coef, b) in enumerate(st.terms):
+                        c = 1.0 if coef is None else coef
+                        if k == 0:
+                            N.call(f"cgp_axpby_{sfx}", c, N.ptr(bufs[b]), 0.0, None, N.ptr(dst),
+                                   n * ne, stream)
+                        else:
+                            N.call(f"cgp_axpby_{sfx}", 1.0, N.ptr(dst), c, N.ptr(bufs[b]),
+                                   N.ptr(dst), n * ne, stream)
+                else:
+                    raise AssertionError(st.fn)
+                for b in st.free:
+                    del bufs[b]
+        return out

@@ -244,6 +244,97 @@ int cgp_var_erf_f32(const float* xx, const float* yy, int64_t n1, int64_t n2, in
                     int32_t same, float* xx_out, float* yy_out, void* stream);
 
 /*
+ * Position-pair maps: networks that end in global average pooling (additions to ABI 12: no
+ * struct or existing entry point changed; no reference counterpart, the reference has no
+ * pooling layer).  A pooled head averages the covariance of every pixel p of
+ * x_i with every pixel q of y_j, so the recursion carries S[p, q] per pair instead of one
+ * [h][w] map.  Layout of a position-pair map of an h×w value, dense:
+ *
+ *     S[m][p_row][q_row][p_col][q_col]        (h·w)² elements per pair, at most 2^30
+ *
+ * (the w×w block of one row pair is contiguous).  Pairs are listed by two DEVICE int32
+ * arrays: pair m is (x image pair_i[m], y image pair_j[m]); the entry points cannot check
+ * the indices against the image counts, the caller does.  Variance maps are the per-image
+ * maps of the entry points above, [n][h·w], indexed xx[pair_i[m]][p] and yy[pair_j[m]][q].
+ * With `same` (y is x) the reference's override of a nonlinearity (kernels.py:155-162)
+ * applies where both arguments are one pre-activation: pair_i[m] == pair_j[m] and p == q;
+ * every other element, p != q of a self pair included, takes the ordinary map.  Every
+ * kernel sums in a fixed order and uses no atomics: a pair's result depends on that pair's
+ * data only, so it does not change with the rest of the pair list or from run to run.
+ */
+#define CGP_COV_NONE 0
+#define CGP_COV_RELU 1   /* the map of cgp_relu_* (closed form, or CGP_FLAG_EXACT_RELU) */
+#define CGP_COV_ERF 2    /* the map of cgp_erf_* */
+/* S[m][p, q] = mean_c x[pair_i[m]][c][p]·y[pair_j[m]][c][q]; x: [n1][c][h·w], y likewise;
+ * out: [npairs] maps.  Summed over c like cgp_moments_var_*. */
+int cgp_cov_moments_f64(const double* x, const double* y, const int32_t* pair_i,
+                        const int32_t* pair_j, int64_t npairs, int32_t c, int32_t h, int32_t w,
+                        double* out, void* stream);
+int cgp_cov_moments_f32(const float* x, const float* y, const int32_t* pair_i,
+                        const int32_t* pair_j, int64_t npairs, int32_t c, int32_t h, int32_t w,
+                        float* out, void* stream);
+/*
+ * Conv2d on position-pair maps: the stencil of cgp_conv_* along the diagonal, p and q
+ * shifted by the same tap,
+ *   out[m][p, q] = weight · Σ_{a,b<taps} in[m][(p_row·s+off+a·d, p_col·s+off+b·d),
+ *                                           (q_row·s+off+a·d, q_col·s+off+b·d)] + bias
+ * with a term zero when either pixel leaves the h×w map; column taps are summed first,
+ * then row taps, like cgp_conv_*'s generic kernel.  Then, optionally, the nonlinearity
+ * `post` with xx / yy = the variances of the conv output, and `+ addend` last (a separate
+ * rounding).  out must not be in (out == addend is allowed).  One workgroup stages `taps`
+ * w×w blocks: taps·w²·itemsize must not exceed 64 KB.  A 1×1 value (h = w = 1: one element
+ * per pair) is a map like any other, which is how a Conv2d after the pool runs.
+ */
+typedef struct cgp_cov_conv_args {
+    const void* in;          /* [npairs][h][h][w][w] */
+    void* out;               /* [npairs][ho][ho][wo][wo] */
+    const void* addend;      /* like out, or NULL */
+    const void* xx;          /* post != CGP_COV_NONE: [n1][ho][wo], else unused */
+    const void* yy;          /* post != CGP_COV_NONE: [n2][ho][wo] (same: may be xx) */
+    const int32_t* pair_i;   /* device [npairs]; read only with a post-nonlinearity */
+    const int32_t* pair_j;
+    int64_t npairs;
+    int32_t h, w, ho, wo;
+    int32_t taps, offset, stride, dilation;   /* as cgp_conv_args */
+    int32_t post;            /* CGP_COV_* */
+    int32_t same;
+    int32_t flags;           /* CGP_FLAG_EXACT_RELU */
+    int32_t reserved;
+    double weight, bias;
+} cgp_cov_conv_args;
+size_t cgp_cov_conv_args_size(void);
+int cgp_cov_conv_f64(const cgp_cov_conv_args* args, void* stream);
+int cgp_cov_conv_f32(const cgp_cov_conv_args* args, void* stream);
+/*
+ * A standalone ReLU or erf on position-pair maps, out = map(in) [+ addend].  In-place
+ * (out == in) is allowed: every element is read and written by one thread.
+ */
+typedef struct cgp_cov_nonlin_args {
+    const void* in;          /* [npairs][h][h][w][w] */
+    void* out;
+    const void* addend;      /* like out, or NULL */
+    const void* xx;          /* [n1][h][w] variances at the nonlinearity's input */
+    const void* yy;          /* [n2][h][w] (same: may be xx) */
+    const int32_t* pair_i;   /* device [npairs] */
+    const int32_t* pair_j;
+    int64_t npairs;
+    int32_t h, w;
+    int32_t kind;            /* CGP_COV_RELU or CGP_COV_ERF */
+    int32_t same;
+    int32_t flags;           /* CGP_FLAG_EXACT_RELU (ReLU only) */
+    int32_t reserved;
+} cgp_cov_nonlin_args;
+size_t cgp_cov_nonlin_args_size(void);
+int cgp_cov_nonlin_f64(const cgp_cov_nonlin_args* args, void* stream);
+int cgp_cov_nonlin_f32(const cgp_cov_nonlin_args* args, void* stream);
+/*
+ * GlobalAvgPool: out[m] = mean of the n elements of pair m's map (n = (h·w)²), accumulated
+ * in double for both types, one workgroup per pair, fixed order.
+ */
+int cgp_cov_pool_f64(const double* in, int64_t npairs, int64_t n, double* out, void* stream);
+int cgp_cov_pool_f32(const float* in, int64_t npairs, int64_t n, float* out, void* stream);
+
+/*
  * out = alpha·a + beta·b (b may be NULL: out = alpha·a), n elements.  The unfused form
  * of Sum (alpha = beta = 1, kernel_patch.py:43-63) and Mixture (kernels.py:220-225).
  * Products and the sum are rounded separately (no FMA contraction), like torch.
