@@ -45,7 +45,7 @@ class ConvArgs(ctypes.Structure):
         ("h", _i32), ("w", _i32), ("ho", _i32), ("wo", _i32),
         ("taps", _i32), ("offset", _i32), ("stride", _i32), ("dilation", _i32),
         ("channels", _i32), ("pre", _i32), ("post", _i32), ("same", _i32), ("diag", _i32),
-        ("maps_per_block", _i32), ("flags", _i32), ("reserved", _i32),
+        ("maps_per_block", _i32), ("flags", _i32), ("max_groups", _i32),
         ("weight", _f64), ("bias", _f64),
     ]
 
@@ -173,6 +173,8 @@ SIGNATURES = {
     "cgp_moments_var_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "cgp_conv_f64": (_i32, [ctypes.POINTER(ConvArgs), _vp]),
     "cgp_conv_f32": (_i32, [ctypes.POINTER(ConvArgs), _vp]),
+    "cgp_conv_plan_f64": (_i32, [ctypes.POINTER(ConvArgs), ctypes.POINTER(_i32)]),
+    "cgp_conv_plan_f32": (_i32, [ctypes.POINTER(ConvArgs), ctypes.POINTER(_i32)]),
     "cgp_relu_f64": (_i32, [ctypes.POINTER(ReluArgs), _vp]),
     "cgp_relu_f32": (_i32, [ctypes.POINTER(ReluArgs), _vp]),
     "cgp_relu_ntk_args_size": (ctypes.c_size_t, []),

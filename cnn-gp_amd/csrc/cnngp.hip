@@ -1282,27 +1282,49 @@ int conv_out_check(const cgp_conv_args* a) {
     if (a->post == CGP_POST_RELU && (!a->post_xx || !a->post_yy))
         return fail(CGP_EINVAL, "conv: POST_RELU needs post_xx/post_yy");
     if (a->maps_per_block < 0) return fail(CGP_EINVAL, "conv: maps_per_block < 0");
+    if (a->max_groups < 0) return fail(CGP_EINVAL, "conv: max_groups < 0");
     return CGP_OK;
 }
 
 // persistent grid: exactly as many workgroups as can be resident at once (registers and
-// LDS both counted by the occupancy query), so no workgroup starts late
-template <typename T, int TAPS>
-int launch_conv(const ConvP<T>& p, size_t lds, hipStream_t s) {
+// LDS both counted by the occupancy query), so no workgroup starts late; max_groups > 0
+// (cgp_conv_args.max_groups, a test / A-B knob) caps it, so a workgroup walks more chunks
+template <class K>
+long long conv_grid(K kern, size_t lds, long long nchunks, int max_groups) {
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, conv_cov_kernel<T, TAPS>, kBlock,
-                                                     lds) != hipSuccess || per_cu < 1) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, lds) != hipSuccess ||
+        per_cu < 1) {
         (void)hipGetLastError();
         per_cu = 1;
     }
-    const long long grid = std::min<long long>(p.nchunks, (long long)per_cu * device_cus());
+    long long grid = std::min<long long>(nchunks, (long long)per_cu * device_cus());
+    if (max_groups > 0) grid = std::min<long long>(grid, max_groups);
+    return grid;
+}
+
+// cgp_conv_plan_*: the launch is described instead of made.  `plan` travels through the
+// same dispatch as a launch and is filled where the launch would happen, from the values
+// the launch would use.
+inline int conv_plan_fill(int32_t* plan, int kernel, int mpc, long long nchunks,
+                          long long grid) {
+    plan[0] = kernel;
+    plan[1] = mpc;
+    plan[2] = (int32_t)nchunks;
+    plan[3] = (int32_t)grid;
+    return CGP_OK;
+}
+
+template <typename T, int TAPS>
+int launch_conv(const ConvP<T>& p, size_t lds, int max_groups, int32_t* plan, hipStream_t s) {
+    const long long grid = conv_grid(conv_cov_kernel<T, TAPS>, lds, p.nchunks, max_groups);
+    if (plan) return conv_plan_fill(plan, 0, p.mpb, p.nchunks, grid);
     hipLaunchKernelGGL((conv_cov_kernel<T, TAPS>), dim3((unsigned)grid), dim3(kBlock), lds, s,
                        p);
     return check_launch("conv_cov_kernel");
 }
 
 template <typename T, class G, int PRE, bool POST, bool ADD>
-int launch_geo(const cgp_conv_args* a, hipStream_t s) {
+int launch_geo(const cgp_conv_args* a, int32_t* plan, hipStream_t s) {
     using L = GeoLayout<T, G>;
     GeoP<T> p;
     p.in = static_cast<const T*>(a->in);
@@ -1326,30 +1348,26 @@ int launch_geo(const cgp_conv_args* a, hipStream_t s) {
     p.bias = (T)a->bias;
     const size_t lds = (size_t)L::ELEMS * sizeof(T);
     auto kern = conv_geo_kernel<T, G, PRE, POST, ADD>;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, lds) != hipSuccess ||
-        per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    const long long grid = std::min<long long>(p.nchunks, (long long)per_cu * device_cus());
+    const long long grid = conv_grid(kern, lds, p.nchunks, a->max_groups);
+    if (plan) return conv_plan_fill(plan, 1, L::MB, p.nchunks, grid);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kBlock), lds, s, p);
     return check_launch("conv_geo_kernel");
 }
 
 // the fused (pre, post, add) combinations the program fuser emits
 template <typename T, class G>
-int launch_geo_mode(const cgp_conv_args* a, hipStream_t s, bool* handled) {
+int launch_geo_mode(const cgp_conv_args* a, int32_t* plan, hipStream_t s,
+                    bool* handled) {
     const bool post = a->post == CGP_POST_RELU, add = a->addend != nullptr;
     *handled = true;
     switch (a->pre * 4 + post * 2 + add) {
-        case 0: return launch_geo<T, G, CGP_PRE_NONE, false, false>(a, s);
-        case 2: return launch_geo<T, G, CGP_PRE_NONE, true, false>(a, s);
-        case 1: return launch_geo<T, G, CGP_PRE_NONE, false, true>(a, s);
-        case 3: return launch_geo<T, G, CGP_PRE_NONE, true, true>(a, s);
-        case 6: return launch_geo<T, G, CGP_PRE_RELU, true, false>(a, s);
-        case 10: return launch_geo<T, G, CGP_PRE_MOMENTS, true, false>(a, s);
-        case 8: return launch_geo<T, G, CGP_PRE_MOMENTS, false, false>(a, s);
+        case 0: return launch_geo<T, G, CGP_PRE_NONE, false, false>(a, plan, s);
+        case 2: return launch_geo<T, G, CGP_PRE_NONE, true, false>(a, plan, s);
+        case 1: return launch_geo<T, G, CGP_PRE_NONE, false, true>(a, plan, s);
+        case 3: return launch_geo<T, G, CGP_PRE_NONE, true, true>(a, plan, s);
+        case 6: return launch_geo<T, G, CGP_PRE_RELU, true, false>(a, plan, s);
+        case 10: return launch_geo<T, G, CGP_PRE_MOMENTS, true, false>(a, plan, s);
+        case 8: return launch_geo<T, G, CGP_PRE_MOMENTS, false, false>(a, plan, s);
     }
     *handled = false;
     return CGP_OK;
@@ -1357,7 +1375,7 @@ int launch_geo_mode(const cgp_conv_args* a, hipStream_t s, bool* handled) {
 
 // compile-time-geometry launch; *handled = false when the shape/mode is not in the table
 template <typename T>
-int conv_geo_impl(const cgp_conv_args* a, void* stream, bool* handled) {
+int conv_geo_impl(const cgp_conv_args* a, int32_t* plan, void* stream, bool* handled) {
     *handled = false;
     if (a->dilation != 1 || a->maps_per_block != 0 || (a->flags & CGP_FLAG_EXACT_RELU))
         return CGP_OK;
@@ -1365,19 +1383,19 @@ int conv_geo_impl(const cgp_conv_args* a, void* stream, bool* handled) {
 #define CGP_GEO_CASE(h_, w_, ho_, wo_, k_, s_, o_)                                         \
     if (a->h == h_ && a->w == w_ && a->ho == ho_ && a->wo == wo_ && a->taps == k_ &&       \
         a->stride == s_ && a->offset == o_)                                               \
-        return launch_geo_mode<T, Geo<h_, w_, ho_, wo_, k_, s_, o_>>(a, s, handled);
+        return launch_geo_mode<T, Geo<h_, w_, ho_, wo_, k_, s_, o_>>(a, plan, s, handled);
     CGP_GEOMETRIES(CGP_GEO_CASE)
 #undef CGP_GEO_CASE
     return CGP_OK;
 }
 
 template <typename T>
-int conv_impl(const cgp_conv_args* a, void* stream) {
+int conv_impl(const cgp_conv_args* a, void* stream, int32_t* plan = nullptr) {
     int rc = conv_out_check(a);
     if (rc) return rc;
     if (!(a->flags & CGP_FLAG_GENERIC_CONV)) {
         bool handled = false;
-        rc = conv_geo_impl<T>(a, stream, &handled);
+        rc = conv_geo_impl<T>(a, plan, stream, &handled);
         if (rc || handled) return rc;
     }
     const int hw = a->h * a->w;
@@ -1440,13 +1458,13 @@ int conv_impl(const cgp_conv_args* a, void* stream) {
     const size_t lds = lds_of(mpb);
     hipStream_t s = as_stream(stream);
     switch (a->taps) {
-        case 1: return launch_conv<T, 1>(p, lds, s);
-        case 2: return launch_conv<T, 2>(p, lds, s);
-        case 3: return launch_conv<T, 3>(p, lds, s);
-        case 4: return launch_conv<T, 4>(p, lds, s);
-        case 5: return launch_conv<T, 5>(p, lds, s);
-        case 7: return launch_conv<T, 7>(p, lds, s);
-        default: return launch_conv<T, 0>(p, lds, s);
+        case 1: return launch_conv<T, 1>(p, lds, a->max_groups, plan, s);
+        case 2: return launch_conv<T, 2>(p, lds, a->max_groups, plan, s);
+        case 3: return launch_conv<T, 3>(p, lds, a->max_groups, plan, s);
+        case 4: return launch_conv<T, 4>(p, lds, a->max_groups, plan, s);
+        case 5: return launch_conv<T, 5>(p, lds, a->max_groups, plan, s);
+        case 7: return launch_conv<T, 7>(p, lds, a->max_groups, plan, s);
+        default: return launch_conv<T, 0>(p, lds, a->max_groups, plan, s);
     }
 }
 
@@ -1822,6 +1840,14 @@ int cgp_conv_f64(const cgp_conv_args* args, void* stream) {
 }
 int cgp_conv_f32(const cgp_conv_args* args, void* stream) {
     return conv_impl<float>(args, stream);
+}
+int cgp_conv_plan_f64(const cgp_conv_args* args, int32_t out[4]) {
+    if (!out) return fail(CGP_EINVAL, "conv plan: out is NULL");
+    return conv_impl<double>(args, nullptr, out);
+}
+int cgp_conv_plan_f32(const cgp_conv_args* args, int32_t out[4]) {
+    if (!out) return fail(CGP_EINVAL, "conv plan: out is NULL");
+    return conv_impl<float>(args, nullptr, out);
 }
 int cgp_relu_f64(const cgp_relu_args* args, void* stream) {
     return relu_impl<double>(args, stream);

@@ -53,7 +53,8 @@ extern "C" {
                                   (correctly rounded 1/sqrt, sqrt, acos, division);
                                   default is the closed form max(c,0)/2 + sqrt(t)·x^1.5·P(x)
                                   of csrc/relu_poly.h, within 1e-14 of the exact map */
-#define CGP_FLAG_GENERIC_CONV 2  /* force the generic conv kernel (tests / A-B timing) */
+#define CGP_FLAG_GENERIC_CONV 2  /* force the generic conv kernel (tests / A-B timing); the
+                                    other such knob is cgp_conv_args.max_groups */
 
 int cgp_abi_version(void);
 /* The factor cgp_net_f64's closed-form ReLU expects on its x-side variance maps (var_x /
@@ -135,11 +136,30 @@ typedef struct cgp_conv_args {
     int32_t same, diag;   /* KernelPatch.same / .diag (kernel_patch.py:4-30) */
     int32_t maps_per_block; /* 0 = library default */
     int32_t flags;          /* CGP_FLAG_* */
-    int32_t reserved;
+    int32_t max_groups;     /* 0 = the library's persistent grid; > 0 caps the grid of either
+                               conv kernel at min(grid, max_groups) workgroups, so each
+                               walks more chunks (tests / A-B runs, like
+                               CGP_FLAG_GENERIC_CONV: it does not change which kernel runs
+                               or any result bit); < 0: CGP_EINVAL.  The field every
+                               library before this addition to ABI 12 called `reserved`
+                               and never read. */
     double weight, bias;
 } cgp_conv_args;
 int cgp_conv_f64(const cgp_conv_args* args, void* stream);
 int cgp_conv_f32(const cgp_conv_args* args, void* stream);
+/*
+ * The launch cgp_conv_* would make for these arguments (an addition to ABI 12; host only:
+ * nothing is launched and no buffer is touched).  Runs the checks of cgp_conv_* with their
+ * return codes, then the dispatch cgp_conv_* itself runs, stopped before the launch:
+ *   out[0]  kernel: 0 = the generic kernel, 1 = the compile-time-geometry kernel
+ *   out[1]  whole maps per chunk
+ *   out[2]  chunks = ceil(nmaps / out[1])
+ *   out[3]  workgroups; each walks chunks blockIdx, blockIdx + out[3], ...
+ * out[3] depends on the device (resident workgroups) unless max_groups caps it below that;
+ * without a device it assumes one workgroup on each of 256 CUs.
+ */
+int cgp_conv_plan_f64(const cgp_conv_args* args, int32_t out[4]);
+int cgp_conv_plan_f32(const cgp_conv_args* args, int32_t out[4]);
 
 /*
  * ReLU covariance map on the pair maps — ReLU.propagate, kernels.py:134-165:
