@@ -1023,6 +1023,144 @@ __device__ __forceinline__ void net_elem(T* __restrict__ lds, const cgp_net_op& 
     }
 }
 
+// ---- MOMENTS of a compiled program: batched image loads (round 10) ---------------------
+// elem_pass keeps the runtime channel loop between a thread's consecutive pixels, so a wave
+// entering a pair pays one dependent global round trip per pixel (7 at 28x28) before its
+// first conv.  With the channel count a compile-time CH the x and y loads of all of a
+// thread's pixels of one channel go out as one block and are waited for once (1 channel: 14
+// loads, one wait; 3 channels: three blocks of 14).  Each pixel still computes x0·y0, then
+// += x_ch·y_ch in channel order, then the same division when channels != 1: bit for bit
+// what elem_pass stores.  CGP_NET_MOMENTS_BATCH=0: elem_pass everywhere (the A/B switch).
+// HO (CGP_NET_MOMENTS_ITEMS, kHoistProg programs whose MOMENTS map has the hoisted conv's
+// output size and pitch): the thread's pixels are those of its column item (rows g3·R3 + k
+// of column c), so pixel k's image offset is hx.px + k·WO·sizeof(T) and its LDS cell
+// hx.at + (DST − dst0) + k·WS: immediates on one register each, one predicate (col_on).
+// Measured (bench.py, ConvNet Kxx 4096², three alternating rounds, profiles/r10): the batch
+// alone -1.9% ms per step, with the column items -3.9%; the wave priority raised around the
+// block (prio_mem / prio_alu) cost 0.9 ms of that and is not applied.
+#ifndef CGP_NET_MOMENTS_BATCH
+#define CGP_NET_MOMENTS_BATCH 1
+#endif
+#ifndef CGP_NET_MOMENTS_ITEMS
+#define CGP_NET_MOMENTS_ITEMS 1
+#endif
+// maps of at most 28x28 pixels: with the 32x32 head's 8 pixels per thread (16 loads a block)
+// the cifar10 head kernel goes from 93 to 101 VGPRs, past the 96 of five waves per SIMD, so
+// that program keeps elem_pass
+#ifndef CGP_NET_MOMENTS_MAXHW
+#define CGP_NET_MOMENTS_MAXHW (28 * 28)
+#endif
+// the values of one block of loads, all present from here on: one wait for the block
+template <typename T, int N>
+__device__ __forceinline__ void loads_fence(T (&v)[N]) {
+    static_assert(N >= 1 && N <= 8, "loads_fence: at most 8 values a side");
+    if constexpr (N == 1) asm volatile("" : "+v"(v[0]));
+    if constexpr (N == 2) asm volatile("" : "+v"(v[0]), "+v"(v[1]));
+    if constexpr (N == 3) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]));
+    if constexpr (N == 4) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+    if constexpr (N == 5)
+        asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]));
+    if constexpr (N == 6)
+        asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]));
+    if constexpr (N == 7)
+        asm volatile(""
+                     : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]),
+                       "+v"(v[6]));
+    if constexpr (N == 8)
+        asm volatile(""
+                     : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]),
+                       "+v"(v[6]), "+v"(v[7]));
+}
+// G: the hoisted conv's geometry (HO), unused otherwise
+template <typename T, int CH, int H_, int W_, int WS, int DST, bool HO, class G>
+__device__ __forceinline__ void moments_batch(T* __restrict__ lds, const NetP<T>& p,
+                                              const Pairs& pr, const ConvHoist<T>& hx) {
+    constexpr int HW = H_ * W_;
+    constexpr int KF = HO ? G::R3 : (HW + kNT - 1) / kNT;   // pixels per thread
+    static_assert(KF <= 8, "moments_batch: at most 8 pixels per thread");
+    const int tid = opaque_tid();
+    // the pair's images as scalar byte bases (elem_pass), one per channel
+    const GP<char> xi = ubase(p.x) + (size_t)pr.i * CH * HW * sizeof(T);
+    const GP<char> yj = ubase(p.y) + (size_t)pr.j * CH * HW * sizeof(T);
+    // pixel k of the thread in a channel plane: byte offset pb plus an immediate step; on the
+    // elementwise layout the ragged last pass has its own, `last` (pixel 0 for an idle thread)
+    unsigned pb, last = 0;
+    bool ok_last = true;
+    if constexpr (HO) {
+        pb = hx.px;
+        asm volatile("" : "+v"(pb));   // the zero extension stays here (net_conv)
+    } else {
+        pb = (unsigned)tid * (unsigned)sizeof(T);
+        if constexpr (HW % kNT != 0) {
+            const int e = (KF - 1) * kNT + tid;
+            ok_last = e < HW;
+            last = (unsigned)(ok_last ? e : 0) * (unsigned)sizeof(T);
+        }
+    }
+    auto ld = [&](GP<char> b, int k) -> T {
+        if constexpr (HO) {
+            return *(GP<T>)(b + (size_t)pb + k * G::WO * (int)sizeof(T));
+        } else {
+            if (HW % kNT != 0 && k == KF - 1) return *(GP<T>)(b + (size_t)last);
+            return *(GP<T>)(b + (size_t)pb + k * kNT * (int)sizeof(T));
+        }
+    };
+    T a[KF];
+#pragma unroll
+    for (int ch = 0; ch < CH; ++ch) {
+        const GP<char> xc = xi + (size_t)ch * HW * sizeof(T);
+        const GP<char> yc = yj + (size_t)ch * HW * sizeof(T);
+        T xv[KF], yv[KF];
+#pragma unroll
+        for (int k = 0; k < KF; ++k) {
+            xv[k] = ld(xc, k);
+            yv[k] = ld(yc, k);
+        }
+        loads_fence(xv);
+        loads_fence(yv);
+#pragma unroll
+        for (int k = 0; k < KF; ++k) a[k] = ch == 0 ? xv[k] * yv[k] : a[k] + xv[k] * yv[k];
+        // the next channel's block goes out after this one is consumed (register budget):
+        // nothing is scheduled across
+        if (ch + 1 < CH) {
+            loads_fence(a);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if constexpr (CH != 1) {   // the channel mean: T(p.channels) as a constant
+#pragma unroll
+        for (int k = 0; k < KF; ++k) a[k] = a[k] / T(CH);
+    }
+    if constexpr (HO) {
+        if (hx.col_on) {
+            const LP<T> at = hx.at + (DST - hx.dst0);
+#pragma unroll
+            for (int k = 0; k < KF; ++k) at[k * WS] = a[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < KF; ++k) {
+            const bool ok = HW % kNT == 0 || k < KF - 1 || ok_last;
+            const int e = ok ? k * kNT + tid : 0;
+            const int r = udiv(e, W_);
+            if (ok) lds[DST + r * WS + (e - r * W_)] = a[k];
+        }
+    }
+}
+// the workgroup-uniform choice of the channel count: 1 and 3 are compiled, any other count
+// runs elem_pass's runtime loop
+template <typename T, bool DU, int H_, int W_, int WS, int DST, bool HO, class G>
+__device__ __forceinline__ void net_moments(T* __restrict__ lds, const cgp_net_op& op,
+                                            const NetP<T>& p, const Pairs& pr,
+                                            const ConvHoist<T>& hx) {
+    if (p.channels == 1)
+        moments_batch<T, 1, H_, W_, WS, DST, HO, G>(lds, p, pr, hx);
+    else if (p.channels == 3)
+        moments_batch<T, 3, H_, W_, WS, DST, HO, G>(lds, p, pr, hx);
+    else
+        net_elem<T, false, DU, CGP_NET_MOMENTS, H_, W_, 1>(lds, op, p, pr);
+}
+
 // Stage boundary (CGP_NET_LOAD / CGP_NET_STORE): the map of each of the NP pairs moves
 // between its slot and the unit's state record, state[(u - ubeg) · code + add + pixel].
 template <typename T, int KIND, int NP>
@@ -1512,6 +1650,19 @@ template <typename T, int PID>
 constexpr bool kHoistProg = CGP_NET_HOIST != 0 && PID >= 0 && sizeof(T) == 8 &&
                             prog_hoist_op(PID < 0 ? 0 : PID) >= 0;
 
+// the geometry of the program's hoisted conv (op HK), or a stand-in where it has none
+struct NoGeo {
+    enum { HO = 0, WO = 1, R3 = 1, NG3 = 0 };
+};
+template <int PID, int HK, bool ON>
+struct HoistGeo {
+    using G = NoGeo;
+};
+template <int PID, int HK>
+struct HoistGeo<PID, HK, true> {
+    using G = typename ProgGeo<PID, HK, 1>::G;
+};
+
 // LEAN: the lean chain (the workgroup found every CONV record lean_rec_ok; prog_recs then
 // holds 2w for the convs that read a halved map)
 template <typename T, bool DU, int NP, int PID, int K, bool LEAN = false>
@@ -1539,6 +1690,17 @@ __device__ __forceinline__ void prog_ops(T* __restrict__ lds, const NetP<T>& p, 
             constexpr bool hoist = kHoistProg<T, PID> && op_separable(o);
             net_conv<T, false, DU, typename ProgGeo<PID, K, NP>::G, kNetPrescale, lean.nocap,
                      lean.half, hoist>(lds, op, p, pr, &hx);
+        } else if constexpr (o.kind == CGP_NET_MOMENTS && NP == 1 && CGP_NET_MOMENTS_BATCH != 0 &&
+                             o.h * o.w <= CGP_NET_MOMENTS_MAXHW) {
+            // on the column items of the hoisted convs where the map has their output's size
+            // and pitch (moments_batch)
+            constexpr int hk = prog_hoist_op(PID);
+            using HG = typename HoistGeo<PID, hk, (hk >= 0)>::G;
+            constexpr ProgOp hc = kProgOps[I.first + (hk < 0 ? 0 : hk)];
+            constexpr bool items = CGP_NET_MOMENTS_ITEMS != 0 && kHoistProg<T, PID> &&
+                                   o.ws_out == hc.ws_out && o.h == HG::HO && o.w == HG::WO &&
+                                   HG::NG3 * HG::R3 == HG::HO;
+            net_moments<T, DU, o.h, o.w, o.ws_out, o.dst, items, HG>(lds, op, p, pr, hx);
         } else if constexpr (o.kind == CGP_NET_RELU || o.kind == CGP_NET_LINEAR ||
                              o.kind == CGP_NET_MOMENTS) {
             net_elem<T, false, DU, o.kind, o.h, o.w, NP>(lds, op, p, pr);
