@@ -22,8 +22,8 @@ from .program import Plan
 # (CGP_VAR_CHAIN=0: the layer-by-layer variance pipeline, one launch per op)
 VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
 
-__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "GlobalAvgPool", "Sequential", "Mixture",
-           "Sum", "resnet_block")
+__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "GlobalAvgPool", "AvgPool2d", "Sequential",
+           "Mixture", "Sum", "resnet_block")
 
 
 def _stream_handle(device):
@@ -127,6 +127,8 @@ class NNGPKernel(nn.Module):
                             float(d["var_weight"]), float(d["var_bias"]),
                             d["_buffers"]["kernel"].dtype))
                 bufs.append(d["_buffers"]["kernel"])
+            elif isinstance(m, AvgPool2d):
+                key.append(("a", d["kernel_size"], d["stride"]))
             elif isinstance(m, Mixture):
                 mixture = True
                 key.append(("m", tuple(m.proportions())))
@@ -188,8 +190,8 @@ class NNGPKernel(nn.Module):
         return self
 
     def set_pool_workspace(self, max_bytes: Optional[int]):
-        """Bytes of device memory the position-pair maps of a model with a GlobalAvgPool
-        (and position_covariance) may take at once; the pairs of a tile run in chunks sized
+        """Bytes of device memory the position-pair maps of a model with a GlobalAvgPool or
+        an AvgPool2d (and position_covariance) may take at once; the pairs of a tile run in chunks sized
         to it, with bit-identical results.  None (default): a quarter of the device's free
         memory, as image_variances takes."""
         for m in self.modules():
@@ -270,12 +272,14 @@ class NNGPKernel(nn.Module):
         (and K from forward itself).
         Equivalently Θ = Σ over all Conv2d outputs of ⟨∂K_final/∂K_xy^l, K_xy^l⟩ at fixed
         variances.  Always evaluated layer by layer (program.ntk_steps: the whole-network
-        kernel carries one map); honours set_exact_relu.  A model with a GlobalAvgPool
-        raises NotImplementedError (Θ on position-pair maps: DESIGN §8)."""
+        kernel carries one map); honours set_exact_relu.  A model with a GlobalAvgPool or
+        an AvgPool2d raises NotImplementedError (Θ on position-pair maps: DESIGN §8)."""
         y, same, diag, empty = self._prologue(x, y, same, diag)
-        if self._plan(x.size(2), x.size(3)).pool is not None:
-            from .program import POOL_RULE_NTK
-            raise NotImplementedError(POOL_RULE_NTK)
+        plan = self._plan(x.size(2), x.size(3))
+        if plan.pool is not None:
+            from .program import AVGPOOL_RULE_NTK, POOL_RULE_NTK
+            avg = any(o.kind == "avgpool" for o in plan.prog.ops)
+            raise NotImplementedError(AVGPOOL_RULE_NTK if avg else POOL_RULE_NTK)
         if empty is not None:
             return (empty, empty.clone()) if return_nngp else empty
         out_device = x.device
@@ -329,7 +333,10 @@ class NNGPKernel(nn.Module):
         plan = self._plan(h, w)
         sfx = Plan._sfx(x.dtype)
         lib = N.load()
-        if plan.pool is not None:                                # GlobalAvgPool: DESIGN §3.3
+        if plan.pool is not None:                 # GlobalAvgPool, AvgPool2d: DESIGN §3.3, §3.4
+            if plan.final_hw != (1, 1):                          # kernels.py:53-57
+                raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
+                                   " per pair, not 1x1: add a final Conv2d covering the map")
             r, pi, pj = self._run_pool(plan, plan.pool, x, y, same, diag, stream)
             if diag:
                 return r.view(n1)
@@ -405,16 +412,25 @@ class NNGPKernel(nn.Module):
             pi = torch.arange(n1, device=dev).repeat_interleave(n2)
             pj = torch.arange(n2, device=dev).repeat(n1)
         var = {}
-        if ps.need_var:
+        ws = getattr(self, "_cgp_pool_ws", None)
+        if ps.need_var - ps.self_var:
             # per-image variances of the inputs (kernels.py:48-49), then of every value a
             # nonlinearity reads: the layer path's own pipeline
             var0 = torch.empty((n1 + n2, h, w), dtype=x.dtype, device=dev)
             N.call(f"cgp_moments_var_{Plan._sfx(x.dtype)}", N.ptr(x), N.ptr(y), n1, n2, c,
                    h * w, N.ptr(var0[:n1]), N.ptr(var0[n1:]), stream)
             var = plan.run_variances(var0[:n1], var0[n1:], n1, n2, same, stream,
-                                     need=set(ps.need_var))
+                                     need=set(ps.need_var - ps.self_var))
+        if ps.self_var:
+            # downstream of an AvgPool2d the variances are the p = q diagonals of the images'
+            # self position-pair maps: the same launches over the pairs (i, i)
+            sx = plan.run_self_variances(x, {v: m[0] for v, m in var.items()}, stream, ps, ws)
+            sy = sx if same else \
+                plan.run_self_variances(y, {v: m[1] for v, m in var.items()}, stream, ps, ws)
+            var = dict(var)
+            var.update({v: (sx[v], sy[v]) for v in ps.self_var})
         r = plan.run_pairs_pool(x, y, var, pi.to(torch.int32), pj.to(torch.int32), same, stream,
-                                ps, getattr(self, "_cgp_pool_ws", None))
+                                ps, ws)
         return r, pi, pj
 
     def position_covariance(self, x, y=None, same=None, diag=False):
@@ -605,6 +621,26 @@ class GlobalAvgPool(NNGPKernel):
 
     def layers(self):
         return 0
+
+
+class AvgPool2d(NNGPKernel):
+    """Windowed average pooling (no reference counterpart; the 2x2 pools between the blocks
+    of the Myrtle and LAP networks), torch.nn.AvgPool2d without padding: the output is
+    floor((H - kernel_size)/stride) + 1 per side, ``stride`` defaulting to ``kernel_size``.
+    On position-pair maps S'[p, q] is the mean of S over the window of p times the window of
+    q; the model runs on them like one with a GlobalAvgPool, which may follow.
+    Without one the final value must be 1x1, e.g. through a dense Conv2d(H', padding=0)."""
+
+    def __init__(self, kernel_size, stride=None):
+        super().__init__()
+        self.kernel_size = kernel_size
+        self.stride = kernel_size if stride is None else stride
+
+    def layers(self):
+        return 0
+
+    def extra_repr(self):
+        return f"kernel_size={self.kernel_size}, stride={self.stride}"
 
 
 class Sequential(NNGPKernel):

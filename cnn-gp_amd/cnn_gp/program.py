@@ -11,6 +11,8 @@ whole [N1·N2, 1, H, W] covariance tensor.  Here the tree is flattened once into
     v  = add[(coef, u), ...]         Sum (kernels.py:252-254) / Mixture (:220-225)
     v  = pool(u)                     GlobalAvgPool (no reference counterpart; DESIGN §3.3:
                                      such a program runs on position-pair maps, pool_steps)
+    v  = avgpool(u, k, stride)       AvgPool2d (no reference counterpart; DESIGN §3.4: on
+                                     position-pair maps as well)
 
 and then split into two device pipelines:
 
@@ -51,11 +53,18 @@ class ConvGeom:
 
 
 @dataclasses.dataclass
+class PoolGeom:
+    """An AvgPool2d's window: kernel_size and stride (no padding)."""
+    taps: int
+    stride: int
+
+
+@dataclasses.dataclass
 class Op:
-    kind: str                              # 'conv' | 'relu' | 'erf' | 'add' | 'pool' | 'moments'
+    kind: str              # 'conv' | 'relu' | 'erf' | 'add' | 'pool' | 'avgpool' | 'moments'
     dst: int
     src: Optional[int] = None
-    geom: Optional[ConvGeom] = None
+    geom: Optional[object] = None          # conv: ConvGeom, avgpool: PoolGeom
     shape_in: tuple = (0, 0)
     shape_out: tuple = (0, 0)
     terms: list = dataclasses.field(default_factory=list)   # add: [(coef|None, value)]
@@ -117,6 +126,18 @@ def conv_out_hw(mod, h: int, w: int):
     return ho, wo
 
 
+def avgpool_out_hw(mod, h: int, w: int):
+    """torch.nn.AvgPool2d's output size without padding: floor((h - k)/s) + 1 per side."""
+    k, s = int(mod.kernel_size), int(mod.stride)
+    if k < 1 or s < 1:
+        raise ValueError(f"AvgPool2d(kernel_size={k}, stride={s}): both must be at least 1")
+    ho, wo = (h - k) // s + 1, (w - k) // s + 1
+    if ho <= 0 or wo <= 0:
+        raise RuntimeError(f"AvgPool2d(kernel_size={k}, stride={s}) produces an empty output "
+                           f"from a {h}x{w} input")
+    return ho, wo
+
+
 def _emit(prog: Program, mod, v: int) -> int:
     """Append the ops of `mod` applied to value v; return the output value."""
     from . import kernels as K
@@ -140,6 +161,13 @@ def _emit(prog: Program, mod, v: int) -> int:
     if isinstance(mod, K.GlobalAvgPool):
         out = prog.new_value((1, 1))
         prog.ops.append(Op("pool", out, src=v, shape_in=prog.shapes[v], shape_out=(1, 1)))
+        return out
+    if isinstance(mod, K.AvgPool2d):
+        h, w = prog.shapes[v]
+        ho, wo = avgpool_out_hw(mod, h, w)
+        out = prog.new_value((ho, wo))
+        prog.ops.append(Op("avgpool", out, src=v, shape_in=(h, w), shape_out=(ho, wo),
+                           geom=PoolGeom(int(mod.kernel_size), int(mod.stride))))
         return out
     if isinstance(mod, K.Sequential):
         for m in mod.mods:
@@ -388,6 +416,10 @@ POOL_RULE_CONV = ("a Conv2d downstream of a GlobalAvgPool must keep the value 1x
                   "(e.g. Conv2d(1, var_weight=..., var_bias=...))")
 POOL_RULE_NTK = ("ntk: the neural tangent kernel of a model with a GlobalAvgPool is not "
                  "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
+AVGPOOL_RULE_GLOBAL = ("an AvgPool2d downstream of a GlobalAvgPool is not implemented: the "
+                       "value there is 1x1 per pair, with no window to average (DESIGN §8)")
+AVGPOOL_RULE_NTK = ("ntk: the neural tangent kernel of a model with an AvgPool2d is not "
+                    "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
 
 
 @dataclasses.dataclass
@@ -400,6 +432,8 @@ class PoolStep:
     fn "nonlin":  dst = relu / erf (``post``) of src, variances of value ``var``
                   [+ addend]                                             cgp_cov_nonlin_*
     fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
+    fn "avgpool": dst = mean of src over the windows of p and of q (op.geom)
+                                                                         cgp_covmap_avgpool_*
     fn "axpby":   dst = Σ coef·buffer over ``terms`` (coef None: 1)      cgp_axpby_*
     ``free``: the buffers nothing reads after this launch."""
     fn: str
@@ -427,6 +461,14 @@ class PoolSteps:
     final: int
     need_var: frozenset  # values whose per-image variance maps the nonlinearities read
     peak: int           # elements per pair live at the fullest launch
+    # AvgPool2d: the values of the unfused program at or downstream of one, the
+    # values of need_var among them -- their variance maps are the p = q diagonals of the
+    # images' self maps, extracted by a pass of steps[:self_last + 1] over the pairs (i, i)
+    # (run_self_variances) -- and the index of the step that writes the last of those
+    # (-1: no self pass)
+    avgpooled: frozenset = frozenset()
+    self_var: frozenset = frozenset()
+    self_last: int = -1
 
     def elems(self, b) -> int:
         h, w = self.shapes[b]
@@ -434,16 +476,26 @@ class PoolSteps:
 
 
 def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps:
-    """The launches of a program with a GlobalAvgPool, over the program fused with rules 1
-    and 2 (conv with a ReLU post-stage, a two-term Sum as an addend).  Values upstream of
-    the pool are position-pair maps S[p, q]; downstream they are 1x1 per pair, and only
-    linear ops may follow (they read no variances).  ``body``: the program has no pool and
-    its final value is a map (NNGPKernel.position_covariance).
+    """The launches of a program with a GlobalAvgPool or an AvgPool2d, over the program
+    fused with rules 1 and 2 (conv with a ReLU post-stage, a two-term Sum as an addend).
+    Values upstream of the GlobalAvgPool are position-pair maps S[p, q]; downstream they are
+    1x1 per pair, and only linear ops may follow (they read no variances).  ``body``: the
+    program has no GlobalAvgPool and its final value is a map (position_covariance, and a
+    model with an AvgPool2d that ends in a dense readout).
 
-    Raises NotImplementedError naming the rule for a ReLU / Erf after a pool and for a path
-    that does not pass exactly one pool."""
+    A conv downstream of an AvgPool2d keeps its ReLU as a launch of its own: the ReLU's
+    variances are the diagonal of the conv's output on the self pairs, which has to exist
+    as a map to be read.
+
+    Raises NotImplementedError naming the rule for a ReLU / Erf or an AvgPool2d after a
+    GlobalAvgPool and for a path that does not pass exactly one GlobalAvgPool."""
     pooled = {v0: False}
+    avgpooled = {v0: False}
     for op in prog.ops:
+        if op.kind == "add":
+            avgpooled[op.dst] = any(avgpooled[t] for _, t in op.terms)
+        else:
+            avgpooled[op.dst] = op.kind == "avgpool" or avgpooled[op.src]
         if op.kind in ("relu", "erf"):
             if pooled[op.src]:
                 raise NotImplementedError(POOL_RULE_NONLIN)
@@ -455,6 +507,10 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
             if pooled[op.src]:
                 raise NotImplementedError(POOL_RULE_ONE)
             pooled[op.dst] = True
+        elif op.kind == "avgpool":
+            if pooled[op.src]:
+                raise NotImplementedError(AVGPOOL_RULE_GLOBAL)
+            pooled[op.dst] = False
         elif op.kind == "conv":
             if pooled[op.src] and tuple(op.shape_out) != (1, 1):
                 raise NotImplementedError(POOL_RULE_CONV)
@@ -471,7 +527,11 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
 
     steps = [PoolStep("moments", v0)]
     for op in fuse(prog, v0, vf, True, pre_relu=False, fold_moments=False):
-        if op.kind == "conv":
+        if op.kind == "conv" and op.post == N.CGP_POST_RELU and avgpooled[op.post_var]:
+            steps.append(PoolStep("conv", op.post_var, src=op.src, op=op))
+            steps.append(PoolStep("nonlin", op.dst, src=op.post_var, op=op, post=N.CGP_COV_RELU,
+                                  var=op.post_var, addend=op.addend))
+        elif op.kind == "conv":
             relu = op.post == N.CGP_POST_RELU
             steps.append(PoolStep("conv", op.dst, src=op.src, op=op,
                                   post=N.CGP_COV_RELU if relu else N.CGP_COV_NONE,
@@ -482,6 +542,8 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
                                   var=op.src, addend=op.addend))
         elif op.kind == "pool":
             steps.append(PoolStep("pool", op.dst, src=op.src, op=op))
+        elif op.kind == "avgpool":
+            steps.append(PoolStep("avgpool", op.dst, src=op.src, op=op))
         else:
             steps.append(PoolStep("axpby", op.dst, op=op, terms=list(op.terms)))
     last = {}
@@ -494,7 +556,11 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
                    frozenset(b for b in bufs if not pooled[b]),
                    frozenset(b for b in bufs if pooled[b]),
                    frozenset(v for v, p in pooled.items() if p), vf,
-                   frozenset(st.var for st in steps if st.var is not None), 0)
+                   frozenset(st.var for st in steps if st.var is not None), 0,
+                   frozenset(v for v, a in avgpooled.items() if a))
+    ps.self_var = frozenset(v for v in ps.need_var if avgpooled[v])
+    ps.self_last = max((idx for idx, st in enumerate(steps) if st.dst in ps.self_var),
+                       default=-1)
     live = set()
     for idx, st in enumerate(steps):
         live.add(st.dst)
@@ -538,10 +604,12 @@ class Plan:
         fh, fw = self.prog.shapes[self.vf]
         self.final_hw = (fh, fw)
         self.moments_fused = any(o.pre == N.CGP_PRE_MOMENTS for o in self.pair_ops)
-        # a model with a GlobalAvgPool runs on position-pair maps (run_pairs_pool); its
-        # rejections are raised here, when the program is compiled
-        self.pool = pool_steps(self.prog, self.v0, self.vf) \
-            if any(o.kind == "pool" for o in self.prog.ops) else None
+        # a model with a GlobalAvgPool or an AvgPool2d runs on position-pair maps
+        # (run_pairs_pool); its rejections are raised here, when the program is compiled.
+        # With an AvgPool2d and no GlobalAvgPool the final value is a map (1x1 for forward)
+        kinds = {o.kind for o in self.prog.ops}
+        self.pool = pool_steps(self.prog, self.v0, self.vf, body="pool" not in kinds) \
+            if kinds & {"pool", "avgpool"} else None
 
     # -- helpers -----------------------------------------------------------------------
     @staticmethod
@@ -576,10 +644,12 @@ class Plan:
         keep = {}
         if self.v0 in need:
             keep[self.v0] = vals[self.v0]
-        pooled = self.pool.pooled if self.pool is not None else ()
+        pooled = self.pool.pooled | self.pool.avgpooled if self.pool is not None else ()
         for idx, op in enumerate(ops):
             if op.dst in pooled:
-                continue        # at or after a GlobalAvgPool: linear ops, no variances read
+                # at or after a GlobalAvgPool: linear ops, no variances read; at or after an
+                # AvgPool2d: the recursion is not closed, run_self_variances has them
+                continue
             ho, wo = op.shape_out
             if op.kind == "conv":
                 xin, yin = vals[op.src]
@@ -983,12 +1053,41 @@ class Plan:
             self._body_steps = pool_steps(self.prog, self.v0, self.vf, body=True)
         return self._body_steps
 
+    def run_self_variances(self, x, var, stream, ps=None, max_bytes=None, want=None):
+        """The variance maps [n, h, w] of the values ``want`` (default ps.self_var: what the
+        nonlinearities downstream of an AvgPool2d read) of the images x: the p = q diagonals
+        of the values' position-pair maps on the self pairs (i, i), run with ``same`` so the
+        nonlinearities' override applies there.  The launches are ps.steps up to the last one
+        that writes a wanted value, chunked like run_pairs_pool; a nonlinearity inside reads
+        the diagonal just extracted from its own source.  var: value -> [n, h, w] maps of the
+        values upstream of every AvgPool2d (one side of run_variances' pairs).  A wanted
+        value must be a buffer of ps (the destination of a launch)."""
+        ps = self.pool if ps is None else ps
+        want = ps.self_var if want is None else frozenset(want)
+        if not want <= {st.dst for st in ps.steps}:
+            raise KeyError(f"run_self_variances: {sorted(want)} are not all launch outputs")
+        n = x.shape[0]
+        last = max(k for k, st in enumerate(ps.steps) if st.dst in want)
+        written = {st.dst for st in ps.steps[:last + 1]}
+        out = {v: torch.empty((n,) + tuple(ps.shapes[v]), dtype=x.dtype, device=x.device)
+               for v in (want | ps.self_var) & written}
+        both = {v: (m, m) for v, m in var.items()}
+        both.update({v: (m, m) for v, m in out.items()})
+        idx = torch.arange(n, device=x.device, dtype=torch.int32)
+        self.run_pairs_pool(x, x, both, idx, idx, True, stream, ps, max_bytes, last=last,
+                            diag_out=out)
+        return {v: out[v] for v in want}
+
     def run_pairs_pool(self, x, y, var, pair_i, pair_j, same, stream, ps=None,
-                       max_bytes=None):
+                       max_bytes=None, last=None, diag_out=None):
         """Runs ``ps`` (default: the plan's own pool_steps) over the pairs (pair_i[m],
         pair_j[m]) -- device int32 arrays -- in chunks of pairs; returns the final value of
         every pair as [npairs, elements] (one element per pair after a pool).
-        x, y: images [n, C, H, W]; var: the variance maps of ps.need_var (run_variances).
+        x, y: images [n, C, H, W]; var: the variance maps of ps.need_var (run_variances, and
+        run_self_variances for ps.self_var).  ``last``: run ps.steps[:last + 1] only and
+        return nothing; ``diag_out``: value -> [n, h, w] tensor that takes the p = q diagonal
+        of the value's map of pair m at image pair_i[m] (cgp_covmap_diag_*), right after the
+        launch that writes it.
 
         A chunk takes ps.peak elements per pair at its fullest launch (every buffer is freed
         after its last reader); chunks are sized to stay under ``max_bytes`` (default: a
@@ -1014,15 +1113,18 @@ class Plan:
         # pairs·elements of one launch stay below 2^40 (the entry points count blocks in int32)
         chunk = min(chunk, npairs, max(1, (1 << 40) // max(ps.elems(b) for b in ps.shapes)))
         C = x.shape[1]
-        out = torch.empty((npairs, ps.elems(ps.final)), dtype=x.dtype, device=dev)
+        steps = ps.steps if last is None else ps.steps[:last + 1]
+        diag_out = diag_out or {}
+        out = None if last is not None else \
+            torch.empty((npairs, ps.elems(ps.final)), dtype=x.dtype, device=dev)
         for a in range(0, npairs, chunk):
             n = min(chunk, npairs - a)
             pi, pj = pair_i[a:a + n], pair_j[a:a + n]
             bufs = {}
-            for st in ps.steps:
+            for st in steps:
                 h, w = ps.shapes[st.dst]
                 ne = ps.elems(st.dst)
-                dst = out[a:a + n] if st.dst == ps.final else \
+                dst = out[a:a + n] if out is not None and st.dst == ps.final else \
                     torch.empty((n, ne), dtype=x.dtype, device=dev)
                 bufs[st.dst] = dst
                 if st.fn == "moments":
@@ -1057,6 +1159,13 @@ class Plan:
                     N.check(getattr(lib, f"cgp_cov_pool_{sfx}")(
                         N.ptr(bufs[st.src]), n, ps.elems(st.src), N.ptr(dst), stream),
                         "cgp_cov_pool")
+                elif st.fn == "avgpool":
+                    r = N.CovAvgPoolArgs()
+                    r.in_, r.out, r.npairs = N.ptr(bufs[st.src]), N.ptr(dst), n
+                    (r.h, r.w), r.ho, r.wo = ps.shapes[st.src], h, w
+                    r.k, r.stride = st.op.geom.taps, st.op.geom.stride
+                    N.check(getattr(lib, f"cgp_covmap_avgpool_{sfx}")(r, stream),
+                            "cgp_covmap_avgpool")
                 elif st.fn == "axpby":
                     for k, (coef, b) in enumerate(st.terms):
                         c = 1.0 if coef is None else coef
@@ -1068,6 +1177,10 @@ class Plan:
                                    N.ptr(dst), n * ne, stream)
                 else:
                     raise AssertionError(st.fn)
+                if st.dst in diag_out:
+                    N.check(getattr(lib, f"cgp_covmap_diag_{sfx}")(
+                        N.ptr(dst), N.ptr(pi), n, h, w, N.ptr(diag_out[st.dst]), stream),
+                        "cgp_covmap_diag")
                 for b in st.free:
                     del bufs[b]
         return out

@@ -308,6 +308,147 @@ __global__ __launch_bounds__(kPoolBlock) void cov_pool_kernel(const T* __restric
 }
 
 // ----------------------------------------------------------------------------------
+// AvgPool2d on position-pair maps: p and q move independently,
+//   S'[P, Q][U, V] = k⁻⁴ · Σ_{a,a'<k} Σ_{b,b'<k} S[P·s + a, Q·s + a'][U·s + b, V·s + b']
+// (a conv moves both by one tap).  A workgroup owns `upb` output row pairs
+// (P, Q) of consecutive pairs.  It streams the k² input blocks (P·s + a, Q·s + a') of each,
+// contiguous w×w ranges, one element per lane per block with a thread's loads issued before
+// its adds, sums them elementwise in registers and stores the w×w sums to LDS.  Then every
+// output takes its k×k window of the sums from LDS, is divided once by k⁴ and stored: one
+// contiguous wo×wo range per row pair.  With s >= k every input element is fetched at most
+// once.  All sums are held in T and their order depends on k alone.  Both sums run over the
+// offset pairs in the order  t(0,0), t(0,1) + t(1,0), ..., t(1,1), t(1,2) + t(2,1), ...:
+// an offset pair and its mirror are added to each other first (a + b == b + a in IEEE), so
+// a self pair's map, symmetric bit for bit under p <-> q coming in, is so going out.
+// ----------------------------------------------------------------------------------
+template <typename T>
+struct CovAvgP {
+    const T* in;
+    T* out;
+    long long units;           // npairs·ho·ho row pairs
+    FastDiv dww, dwowo, dwo;
+    int h, w, ho, wo, k, stride, upb;
+    int tab_offset;            // byte offset of the row pairs' base offsets in LDS
+    T k4;
+};
+
+// K: the window edge at compile time (every block's loads of a pass in flight at once), or
+// 0 for p.k at run time (one block's loads in flight at a time)
+template <typename T, int K>
+__global__ __launch_bounds__(kBlock) void cov_avgpool_kernel(const CovAvgP<T> p) {
+    // dynamic LDS: the summed blocks [upb][w·w], then each row pair's element offset in
+    // `in` of its block (P·s, Q·s)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    T* lds = reinterpret_cast<T*>(smem);
+    long long* s_base = reinterpret_cast<long long*>(smem + p.tab_offset);
+    const int tid = threadIdx.x;
+    const int k = K ? K : p.k;
+    const long long u0 = (long long)blockIdx.x * p.upb;
+    const long long urem = p.units - u0;
+    const int nu = urem < p.upb ? (int)urem : p.upb;
+    const int ww = p.w * p.w, wowo = p.wo * p.wo, hoho = p.ho * p.ho;
+    for (int ul = tid; ul < nu; ul += kBlock) {
+        const long long u = u0 + ul;
+        const long long m = u / hoho;
+        const int r = (int)(u - m * hoho);
+        const int pr = r / p.ho, qr = r - pr * p.ho;
+        s_base[ul] = ((m * p.h + pr * p.stride) * p.h + qr * p.stride) * ww;
+    }
+    __syncthreads();
+
+    // ---- stream: the k² blocks of every row pair, summed elementwise into LDS ----
+    const int total = nu * ww;
+    const long long rowstep = (long long)p.h * ww;     // from block (a, a') to (a + 1, a')
+    for (int e0 = tid; e0 < total; e0 += kE * kBlock) {
+        const T* src[kE];
+        T acc[kE];
+#pragma unroll
+        for (int j = 0; j < kE; ++j) {
+            const int e = e0 + j * kBlock;
+            src[j] = p.in;
+            if (e < total) {
+                const unsigned ul = fdiv((unsigned)e, p.dww);
+                src[j] = p.in + s_base[ul] + (e - (int)ul * ww);
+            }
+        }
+        if constexpr (K == 2) {
+            T v[4][kE];
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int j = 0; j < kE; ++j)
+                    v[b][j] = e0 + j * kBlock < total ? src[j][(b >> 1) * rowstep + (b & 1) * ww]
+                                                      : T(0);
+#pragma unroll
+            for (int j = 0; j < kE; ++j) acc[j] = (v[0][j] + (v[1][j] + v[2][j])) + v[3][j];
+        } else {
+            for (int a = 0; a < k; ++a) {
+                const long long o = a * rowstep + (long long)a * ww;
+                T v[kE];
+#pragma unroll
+                for (int j = 0; j < kE; ++j) v[j] = e0 + j * kBlock < total ? src[j][o] : T(0);
+#pragma unroll
+                for (int j = 0; j < kE; ++j) acc[j] = a == 0 ? v[j] : acc[j] + v[j];
+                for (int a2 = a + 1; a2 < k; ++a2) {
+                    const long long o1 = a * rowstep + (long long)a2 * ww;
+                    const long long o2 = a2 * rowstep + (long long)a * ww;
+                    T v1[kE], v2[kE];
+#pragma unroll
+                    for (int j = 0; j < kE; ++j) {
+                        const bool in = e0 + j * kBlock < total;
+                        v1[j] = in ? src[j][o1] : T(0);
+                        v2[j] = in ? src[j][o2] : T(0);
+                    }
+#pragma unroll
+                    for (int j = 0; j < kE; ++j) acc[j] = acc[j] + (v1[j] + v2[j]);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kE; ++j) {
+            const int e = e0 + j * kBlock;
+            if (e < total) lds[e] = acc[j];
+        }
+    }
+    __syncthreads();
+
+    // ---- window sums over the columns, the one scale, store ----
+    for (int e = tid; e < nu * wowo; e += kBlock) {
+        const unsigned ul = fdiv((unsigned)e, p.dwowo);
+        const int o = e - (int)ul * wowo;
+        const unsigned pc = fdiv((unsigned)o, p.dwo);
+        const int qc = o - (int)pc * p.wo;
+        const T* blk = lds + (int)ul * ww + (int)pc * p.stride * p.w + qc * p.stride;
+        T acc = T(0);
+        for (int b = 0; b < k; ++b) {
+            const T t = blk[b * p.w + b];
+            acc = b == 0 ? t : acc + t;
+            for (int b2 = b + 1; b2 < k; ++b2) acc = acc + (blk[b * p.w + b2] + blk[b2 * p.w + b]);
+        }
+        p.out[(u0 + ul) * wowo + o] = acc / p.k4;
+    }
+}
+
+// ----------------------------------------------------------------------------------
+// out[pi[m]][r][c] = in[m][r][r][c][c]: the p = q diagonal of pair m's map, the variance map
+// of image pi[m] when pair m is (i, i).  A gather of h·w elements per pair.
+// ----------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kBlock) void cov_diag_kernel(const T* __restrict__ in,
+                                                          const int* __restrict__ pi,
+                                                          long long total, int h, int w,
+                                                          T* __restrict__ out) {
+    const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= total) return;
+    const int hw = h * w;
+    const long long m = t / hw;
+    const int rc = (int)(t - m * hw);
+    const int r = rc / w, c = rc - r * w;
+    const long long n = (long long)hw * hw;
+    out[(long long)pi[m] * hw + rc] = in[m * n + ((long long)(r * h + r) * w + c) * w + c];
+}
+
+// ----------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------
 bool bad_map(int h, int w) {
@@ -433,6 +574,74 @@ int cov_pool_impl(const T* in, int64_t npairs, int64_t n, T* out, void* stream) 
     return check_launch("cov_pool_kernel");
 }
 
+template <typename T>
+int cov_avgpool_impl(const cgp_covmap_avgpool_args* a, void* stream) {
+    if (!a || !a->in || !a->out) return fail(CGP_EINVAL, "covmap_avgpool: NULL argument");
+    if (a->in == a->out) return fail(CGP_EINVAL, "covmap_avgpool: out must not be in");
+    if (a->npairs <= 0 || a->npairs >= (1LL << 31) || bad_map(a->h, a->w) ||
+        bad_map(a->ho, a->wo))
+        return fail(CGP_EINVAL, "covmap_avgpool: bad sizes");
+    if (a->k < 1 || a->stride < 1)
+        return fail(CGP_EINVAL, "covmap_avgpool: bad geometry (kernel_size %d, stride %d)", a->k,
+                    a->stride);
+    if (a->k > a->h || a->k > a->w)
+        return fail(CGP_EINVAL, "covmap_avgpool: a %dx%d window does not fit a %dx%d map", a->k,
+                    a->k, a->h, a->w);
+    if (a->ho != (a->h - a->k) / a->stride + 1 || a->wo != (a->w - a->k) / a->stride + 1)
+        return fail(CGP_EINVAL,
+                    "covmap_avgpool: output size %dx%d is not floor((%dx%d - %d)/%d) + 1", a->ho,
+                    a->wo, a->h, a->w, a->k, a->stride);
+    const long long ww = (long long)a->w * a->w;
+    // one row pair's summed block and its base offset
+    const long long unit_bytes = ww * (long long)sizeof(T) + 8;
+    if (unit_bytes + 8 > kMaxLds)
+        return fail(CGP_EINVAL,
+                    "covmap_avgpool: a %dx%d block is %lld bytes, more than the %d of LDS a "
+                    "workgroup holds", a->w, a->w, ww * (long long)sizeof(T), kMaxLds);
+    CovAvgP<T> p;
+    p.in = static_cast<const T*>(a->in);
+    p.out = static_cast<T*>(a->out);
+    p.units = (long long)a->npairs * a->ho * a->ho;
+    p.h = a->h, p.w = a->w, p.ho = a->ho, p.wo = a->wo;
+    p.k = a->k, p.stride = a->stride;
+    p.k4 = (T)((double)a->k * a->k * a->k * a->k);
+    // small maps: several row pairs per workgroup, one full pass of kE loads per thread
+    long long upb = std::max<long long>(1, kChunk / ww);
+    upb = std::min<long long>(upb, kMaxUnits);
+    upb = std::min<long long>(upb, (kMaxLds - 8) / unit_bytes);
+    p.upb = (int)upb;
+    p.tab_offset = (int)((upb * ww * (long long)sizeof(T) + 7) / 8 * 8);
+    p.dww = make_fastdiv((unsigned)ww);
+    p.dwowo = make_fastdiv((unsigned)(a->wo * a->wo));
+    p.dwo = make_fastdiv((unsigned)a->wo);
+    const long long blocks = (p.units + upb - 1) / upb;
+    if (blocks >= (1LL << 31))
+        return fail(CGP_EINVAL, "covmap_avgpool: %lld row pairs", p.units);
+    const size_t lds = (size_t)p.tab_offset + (size_t)upb * 8;
+    hipStream_t s = as_stream(stream);
+    if (a->k == 2)
+        hipLaunchKernelGGL((cov_avgpool_kernel<T, 2>), dim3((unsigned)blocks), dim3(kBlock), lds,
+                           s, p);
+    else
+        hipLaunchKernelGGL((cov_avgpool_kernel<T, 0>), dim3((unsigned)blocks), dim3(kBlock), lds,
+                           s, p);
+    return check_launch("cov_avgpool_kernel");
+}
+
+template <typename T>
+int cov_diag_impl(const T* in, const int32_t* pi, int64_t npairs, int32_t h, int32_t w, T* out,
+                  void* stream) {
+    if (!in || !pi || !out) return fail(CGP_EINVAL, "covmap_diag: NULL argument");
+    if (npairs <= 0 || npairs >= (1LL << 31) || bad_map(h, w))
+        return fail(CGP_EINVAL, "covmap_diag: bad sizes");
+    const long long total = (long long)npairs * h * w;
+    const long long blocks = (total + kBlock - 1) / kBlock;
+    if (blocks >= (1LL << 31)) return fail(CGP_EINVAL, "covmap_diag: %lld elements", total);
+    hipLaunchKernelGGL((cov_diag_kernel<T>), dim3((unsigned)blocks), dim3(kBlock), 0,
+                       as_stream(stream), in, pi, total, h, w, out);
+    return check_launch("cov_diag_kernel");
+}
+
 }  // namespace
 
 extern "C" {
@@ -467,6 +676,22 @@ int cgp_cov_pool_f64(const double* in, int64_t npairs, int64_t n, double* out, v
 }
 int cgp_cov_pool_f32(const float* in, int64_t npairs, int64_t n, float* out, void* stream) {
     return cov_pool_impl<float>(in, npairs, n, out, stream);
+}
+
+size_t cgp_covmap_avgpool_args_size(void) { return sizeof(cgp_covmap_avgpool_args); }
+int cgp_covmap_avgpool_f64(const cgp_covmap_avgpool_args* args, void* stream) {
+    return cov_avgpool_impl<double>(args, stream);
+}
+int cgp_covmap_avgpool_f32(const cgp_covmap_avgpool_args* args, void* stream) {
+    return cov_avgpool_impl<float>(args, stream);
+}
+int cgp_covmap_diag_f64(const double* in, const int32_t* pair_i, int64_t npairs, int32_t h,
+                        int32_t w, double* out, void* stream) {
+    return cov_diag_impl<double>(in, pair_i, npairs, h, w, out, stream);
+}
+int cgp_covmap_diag_f32(const float* in, const int32_t* pair_i, int64_t npairs, int32_t h,
+                        int32_t w, float* out, void* stream) {
+    return cov_diag_impl<float>(in, pair_i, npairs, h, w, out, stream);
 }
 
 }  // extern "C"

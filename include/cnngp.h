@@ -353,6 +353,39 @@ int cgp_cov_nonlin_f32(const cgp_cov_nonlin_args* args, void* stream);
  */
 int cgp_cov_pool_f64(const double* in, int64_t npairs, int64_t n, double* out, void* stream);
 int cgp_cov_pool_f32(const float* in, int64_t npairs, int64_t n, float* out, void* stream);
+/*
+ * AvgPool2d on position-pair maps (additions to ABI 12: no struct or existing entry point
+ * changed).  A windowed average moves p and q independently, unlike a conv:
+ *   out[m][P][Q][U][V] = k⁻⁴ · Σ_{a,a'<k} Σ_{b,b'<k} in[m][P·s+a][Q·s+a'][U·s+b][V·s+b']
+ * with no padding: ho = floor((h - k)/s) + 1 and wo likewise (rows and columns that do not
+ * fill a window are dropped), which the entry point checks.  The k² row blocks are summed
+ * first, then the k×k column window, all in the map's type, and the sum is divided once by
+ * k⁴; k = 1, s = 1 copies the map bit for bit.  Both sums add an offset pair (a, a') to its
+ * mirror (a', a) before anything else, so a map that is symmetric bit for bit under p <-> q
+ * (a self pair's) stays so.  out must not be in.  One workgroup holds a w×w block of sums:
+ * w²·itemsize must not exceed 64 KB.
+ */
+typedef struct cgp_covmap_avgpool_args {
+    const void* in;          /* [npairs][h][h][w][w] */
+    void* out;               /* [npairs][ho][ho][wo][wo] */
+    int64_t npairs;
+    int32_t h, w, ho, wo;
+    int32_t k, stride;       /* kernel_size and stride, both >= 1; k <= h and k <= w */
+} cgp_covmap_avgpool_args;
+size_t cgp_covmap_avgpool_args_size(void);
+int cgp_covmap_avgpool_f64(const cgp_covmap_avgpool_args* args, void* stream);
+int cgp_covmap_avgpool_f32(const cgp_covmap_avgpool_args* args, void* stream);
+/*
+ * The p = q diagonal of position-pair maps: out[pair_i[m]][r][c] = in[m][r][r][c][c], with
+ * in [npairs][h][h][w][w] and out [n][h][w] per-image maps.  Of the self pairs (i, i) of an
+ * image set these are the per-image variance maps of the value (the only way to them
+ * downstream of an AvgPool2d).  Images no pair names are left untouched; the
+ * pair_i[m] must differ from each other.
+ */
+int cgp_covmap_diag_f64(const double* in, const int32_t* pair_i, int64_t npairs, int32_t h,
+                        int32_t w, double* out, void* stream);
+int cgp_covmap_diag_f32(const float* in, const int32_t* pair_i, int64_t npairs, int32_t h,
+                        int32_t w, float* out, void* stream);
 
 /*
  * out = alpha·a + beta·b (b may be NULL: out = alpha·a), n elements.  The unfused form
