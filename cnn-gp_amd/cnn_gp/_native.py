@@ -112,6 +112,17 @@ class CovAvgPoolArgs(ctypes.Structure):
     ]
 
 
+class CorrConvArgs(ctypes.Structure):
+    """Mirror of cgp_corrconv_args (include/cnngp.h)."""
+    _fields_ = [
+        ("in_", _vp), ("out", _vp), ("corr_rows", _vp), ("corr_cols", _vp),
+        ("npairs", _i64),
+        ("h", _i32), ("w", _i32), ("ho", _i32), ("wo", _i32),
+        ("taps", _i32), ("offset", _i32), ("stride", _i32), ("dilation", _i32),
+        ("weight", _f64), ("bias", _f64),
+    ]
+
+
 class NetOp(ctypes.Structure):
     """Mirror of cgp_net_op (include/cnngp.h)."""
     _fields_ = [
@@ -211,6 +222,9 @@ SIGNATURES = {
     "cgp_covmap_avgpool_f32": (_i32, [ctypes.POINTER(CovAvgPoolArgs), _vp]),
     "cgp_covmap_diag_f64": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "cgp_covmap_diag_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "cgp_corrconv_args_size": (ctypes.c_size_t, []),
+    "cgp_corrconv_f64": (_i32, [ctypes.POINTER(CorrConvArgs), _vp]),
+    "cgp_corrconv_f32": (_i32, [ctypes.POINTER(CorrConvArgs), _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_axpby_f32": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_scale_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _f64, _vp]),
@@ -285,6 +299,7 @@ def load():
                 lib.cgp_cov_conv_args_size() != ctypes.sizeof(CovConvArgs) or \
                 lib.cgp_cov_nonlin_args_size() != ctypes.sizeof(CovNonlinArgs) or \
                 lib.cgp_covmap_avgpool_args_size() != ctypes.sizeof(CovAvgPoolArgs) or \
+                lib.cgp_corrconv_args_size() != ctypes.sizeof(CorrConvArgs) or \
                 lib.cgp_net_op_size() != ctypes.sizeof(NetOp) or \
                 lib.cgp_net_args_size() != ctypes.sizeof(NetArgs) or \
                 lib.cgp_var_op_size() != ctypes.sizeof(VarOp) or \

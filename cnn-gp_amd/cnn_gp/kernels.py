@@ -22,8 +22,9 @@ from .program import Plan
 # (CGP_VAR_CHAIN=0: the layer-by-layer variance pipeline, one launch per op)
 VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
 
-__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "GlobalAvgPool", "AvgPool2d", "Sequential",
-           "Mixture", "Sum", "resnet_block")
+__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "GlobalAvgPool", "AvgPool2d",
+           "CorrelatedConv2d", "rbf_corr", "band_corr", "Sequential", "Mixture", "Sum",
+           "resnet_block")
 
 
 def _stream_handle(device):
@@ -129,6 +130,11 @@ class NNGPKernel(nn.Module):
                 bufs.append(d["_buffers"]["kernel"])
             elif isinstance(m, AvgPool2d):
                 key.append(("a", d["kernel_size"], d["stride"]))
+            elif isinstance(m, CorrelatedConv2d):
+                # R lives on the host as tuples: nothing to sync, no in-place edits
+                key.append(("r", d["kernel_size"], d["stride"], d["_padding_arg"], d["padding"],
+                            d["dilation"], float(d["var_weight"]), float(d["var_bias"]),
+                            d["lengthscale"], d["corr_rows"], d["corr_cols"]))
             elif isinstance(m, Mixture):
                 mixture = True
                 key.append(("m", tuple(m.proportions())))
@@ -190,10 +196,10 @@ class NNGPKernel(nn.Module):
         return self
 
     def set_pool_workspace(self, max_bytes: Optional[int]):
-        """Bytes of device memory the position-pair maps of a model with a GlobalAvgPool or
-        an AvgPool2d (and position_covariance) may take at once; the pairs of a tile run in chunks sized
-        to it, with bit-identical results.  None (default): a quarter of the device's free
-        memory, as image_variances takes."""
+        """Bytes of device memory the position-pair maps of a model with a GlobalAvgPool, an
+        AvgPool2d or a CorrelatedConv2d (and position_covariance) may take at once; the pairs
+        of a tile run in chunks sized to it, with bit-identical results.  None (default): a
+        quarter of the device's free memory, as image_variances takes."""
         for m in self.modules():
             m.__dict__["_cgp_pool_ws"] = None if max_bytes is None else int(max_bytes)
         return self
@@ -272,14 +278,16 @@ class NNGPKernel(nn.Module):
         (and K from forward itself).
         Equivalently Θ = Σ over all Conv2d outputs of ⟨∂K_final/∂K_xy^l, K_xy^l⟩ at fixed
         variances.  Always evaluated layer by layer (program.ntk_steps: the whole-network
-        kernel carries one map); honours set_exact_relu.  A model with a GlobalAvgPool or
-        an AvgPool2d raises NotImplementedError (Θ on position-pair maps: DESIGN §8)."""
+        kernel carries one map); honours set_exact_relu.  A model with a GlobalAvgPool, an
+        AvgPool2d or a CorrelatedConv2d raises NotImplementedError (Θ on position-pair maps:
+        DESIGN §8)."""
         y, same, diag, empty = self._prologue(x, y, same, diag)
         plan = self._plan(x.size(2), x.size(3))
         if plan.pool is not None:
-            from .program import AVGPOOL_RULE_NTK, POOL_RULE_NTK
-            avg = any(o.kind == "avgpool" for o in plan.prog.ops)
-            raise NotImplementedError(AVGPOOL_RULE_NTK if avg else POOL_RULE_NTK)
+            from .program import AVGPOOL_RULE_NTK, CORRCONV_RULE_NTK, POOL_RULE_NTK
+            kinds = {o.kind for o in plan.prog.ops}
+            raise NotImplementedError(CORRCONV_RULE_NTK if "corrconv" in kinds else
+                                      AVGPOOL_RULE_NTK if "avgpool" in kinds else POOL_RULE_NTK)
         if empty is not None:
             return (empty, empty.clone()) if return_nngp else empty
         out_device = x.device
@@ -333,7 +341,7 @@ class NNGPKernel(nn.Module):
         plan = self._plan(h, w)
         sfx = Plan._sfx(x.dtype)
         lib = N.load()
-        if plan.pool is not None:                 # GlobalAvgPool, AvgPool2d: DESIGN §3.3, §3.4
+        if plan.pool is not None:     # GlobalAvgPool, AvgPool2d, CorrelatedConv2d: DESIGN §3.3-5
             if plan.final_hw != (1, 1):                          # kernels.py:53-57
                 raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
                                    " per pair, not 1x1: add a final Conv2d covering the map")
@@ -641,6 +649,103 @@ class AvgPool2d(NNGPKernel):
 
     def extra_repr(self):
         return f"kernel_size={self.kernel_size}, stride={self.stride}"
+
+
+def rbf_corr(k, lengthscale):
+    """The k x k float64 matrix exp(-(a - a')²/(2·lengthscale²)) of tap indices a, a': the
+    RBF weight correlation of Garriga-Alonso & van der Wilk 2021 along one axis.
+    lengthscale 0 gives the identity (independent taps, Conv2d), inf all ones (one shared
+    weight, mean pooling)."""
+    k, ls = int(k), float(lengthscale)
+    if k < 1 or not ls >= 0:
+        raise ValueError(f"rbf_corr(k={k}, lengthscale={lengthscale}): k must be at least 1 and "
+                         "the lengthscale non-negative")
+    d2 = (np.arange(k)[:, None] - np.arange(k)[None, :]).astype(np.float64) ** 2
+    if ls == 0:
+        return (d2 == 0).astype(np.float64)
+    return np.exp(-d2 / (2 * ls * ls))
+
+
+def band_corr(k, c):
+    """The k x k float64 matrix 1(|a - a'| <= c): the local average pooling head of Li et al.
+    2019 along one axis (zero padded).  Not positive semi-definite for 0 < c < k - 1."""
+    k, c = int(k), int(c)
+    if k < 1 or c < 0:
+        raise ValueError(f"band_corr(k={k}, c={c}): k must be at least 1 and c non-negative")
+    idx = np.arange(k)
+    return (np.abs(idx[:, None] - idx[None, :]) <= c).astype(np.float64)
+
+
+class CorrelatedConv2d(NNGPKernel):
+    """A conv or readout whose weights are correlated across the taps of one filter (no
+    reference counterpart; Garriga-Alonso & van der Wilk 2021).  With R[δ, δ'] the correlation
+    of taps δ and δ',
+
+        S'[p, q] = (var_weight/k²) · Σ_{δ, δ'} R[δ, δ'] · S[p·s + off + δ·d, q·s + off + δ'·d]
+                   + var_bias
+
+    on position-pair maps; R = I is Conv2d, R = ones at k = H the GlobalAvgPool
+    head, a band at k = H local average pooling.  R is separable: R[(a, b), (a', b')] =
+    R_rows[a, a']·R_cols[b, b'], given either as ``weight_corr=(R_rows, R_cols)``, two
+    symmetric finite k x k array-likes, or as ``lengthscale``: both are rbf_corr(k,
+    lengthscale).  Exactly one of the two is given.  Positive semi-definiteness is not
+    checked (band_corr is not PSD); a non-separable R has no path here.  Geometry and padding
+    rules are Conv2d's, an even "same" kernel keeps its tap offset, and R indexes the k real
+    taps.  The model runs on position-pair maps like one with an AvgPool2d; the scale
+    var_weight/k² is taken in double (there is no float32 kernel buffer)."""
+
+    def __init__(self, kernel_size, stride=1, padding="same", dilation=1, var_weight=1.,
+                 var_bias=0., weight_corr=None, lengthscale=None):
+        super().__init__()
+        k = int(kernel_size)
+        if k < 1:
+            raise ValueError(f"CorrelatedConv2d: kernel_size {kernel_size} must be at least 1")
+        if (weight_corr is None) == (lengthscale is None):
+            raise ValueError("CorrelatedConv2d: give exactly one of weight_corr=(R_rows, R_cols) "
+                             "and lengthscale")
+        if lengthscale is not None:
+            rows = cols = rbf_corr(k, lengthscale)
+            lengthscale = float(lengthscale)
+        else:
+            try:
+                rows, cols = weight_corr
+            except (TypeError, ValueError):
+                raise ValueError("CorrelatedConv2d: weight_corr must be a pair (R_rows, R_cols) "
+                                 "of k x k matrices") from None
+        mats = []
+        for name, r in (("R_rows", rows), ("R_cols", cols)):
+            r = np.array(r, dtype=np.float64)
+            if r.shape != (k, k):
+                raise ValueError(f"CorrelatedConv2d: {name} has shape {r.shape}, not ({k}, {k})")
+            if not np.all(np.isfinite(r)):
+                raise ValueError(f"CorrelatedConv2d: {name} has entries that are not finite")
+            if not np.array_equal(r, r.T):
+                raise ValueError(f"CorrelatedConv2d: {name} is not symmetric")
+            mats.append(tuple(tuple(float(v) for v in row) for row in r))
+        self.kernel_size = k
+        self.stride = stride
+        self.dilation = dilation
+        self.var_weight = var_weight
+        self.var_bias = var_bias
+        self.lengthscale = lengthscale
+        self.corr_rows, self.corr_cols = mats        # immutable float64 tuples, on the host
+        self.kernel_has_row_of_zeros = False
+        self._padding_arg = padding
+        if padding == "same":
+            self.padding = dilation * (k // 2)
+            self.kernel_has_row_of_zeros = k % 2 == 0
+        else:
+            self.padding = padding
+
+    def layers(self):
+        return 1
+
+    def extra_repr(self):
+        corr = f"lengthscale={self.lengthscale}" if self.lengthscale is not None else \
+            "weight_corr=(R_rows, R_cols)"
+        return (f"kernel_size={self.kernel_size}, stride={self.stride}, "
+                f"padding={self.padding}, dilation={self.dilation}, "
+                f"var_weight={self.var_weight}, var_bias={self.var_bias}, {corr}")
 
 
 class Sequential(NNGPKernel):

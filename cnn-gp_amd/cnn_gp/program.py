@@ -13,6 +13,8 @@ whole [N1·N2, 1, H, W] covariance tensor.  Here the tree is flattened once into
                                      such a program runs on position-pair maps, pool_steps)
     v  = avgpool(u, k, stride)       AvgPool2d (no reference counterpart; DESIGN §3.4: on
                                      position-pair maps as well)
+    v  = corrconv(u, geom, R)        CorrelatedConv2d (no reference counterpart; DESIGN §3.5:
+                                     on position-pair maps as well)
 
 and then split into two device pipelines:
 
@@ -60,11 +62,20 @@ class PoolGeom:
 
 
 @dataclasses.dataclass
+class CorrGeom(ConvGeom):
+    """A CorrelatedConv2d: ConvGeom (weight = var_weight/k² in double) plus the two k x k
+    tap correlation matrices, tuples of tuples of float."""
+    corr_rows: tuple = ()
+    corr_cols: tuple = ()
+
+
+@dataclasses.dataclass
 class Op:
-    kind: str              # 'conv' | 'relu' | 'erf' | 'add' | 'pool' | 'avgpool' | 'moments'
+    # 'conv' | 'relu' | 'erf' | 'add' | 'pool' | 'avgpool' | 'corrconv' | 'moments'
+    kind: str
     dst: int
     src: Optional[int] = None
-    geom: Optional[object] = None          # conv: ConvGeom, avgpool: PoolGeom
+    geom: Optional[object] = None   # conv: ConvGeom, avgpool: PoolGeom, corrconv: CorrGeom
     shape_in: tuple = (0, 0)
     shape_out: tuple = (0, 0)
     terms: list = dataclasses.field(default_factory=list)   # add: [(coef|None, value)]
@@ -138,9 +149,29 @@ def avgpool_out_hw(mod, h: int, w: int):
     return ho, wo
 
 
+def corrconv_geometry(mod) -> CorrGeom:
+    """Conv2d's padding rules as tap offsets (conv_geometry) for a CorrelatedConv2d; the
+    scale is var_weight/k² in double."""
+    k, d, s = int(mod.kernel_size), int(mod.dilation), int(mod.stride)
+    if s < 1 or d < 1:
+        raise ValueError(f"CorrelatedConv2d(stride={s}, dilation={d}): both must be at least 1")
+    offset = -int(mod.padding) + (d if mod.kernel_has_row_of_zeros else 0)
+    return CorrGeom(taps=k, offset=offset, stride=s, dilation=d,
+                    weight=float(mod.var_weight) / (k * k), bias=float(mod.var_bias),
+                    extent=k + 1 if mod.kernel_has_row_of_zeros else k,
+                    corr_rows=mod.corr_rows, corr_cols=mod.corr_cols)
+
+
 def _emit(prog: Program, mod, v: int) -> int:
     """Append the ops of `mod` applied to value v; return the output value."""
     from . import kernels as K
+    if isinstance(mod, K.CorrelatedConv2d):
+        h, w = prog.shapes[v]
+        ho, wo = conv_out_hw(mod, h, w)
+        out = prog.new_value((ho, wo))
+        prog.ops.append(Op("corrconv", out, src=v, geom=corrconv_geometry(mod),
+                           shape_in=(h, w), shape_out=(ho, wo)))
+        return out
     if isinstance(mod, K.Conv2d):
         h, w = prog.shapes[v]
         ho, wo = conv_out_hw(mod, h, w)
@@ -266,6 +297,8 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
                 oi = producer(ops, other)
                 if oi is not None and oi > pi:
                     continue                    # the addend must exist before the producer
+                if oi is not None and ops[oi].kind == "corrconv":
+                    continue                    # a Sum with a CorrelatedConv2d runs as axpby
                 if cand == other:
                     continue
                 ops[pi].addend, ops[pi].dst = other, a.dst
@@ -420,6 +453,10 @@ AVGPOOL_RULE_GLOBAL = ("an AvgPool2d downstream of a GlobalAvgPool is not implem
                        "value there is 1x1 per pair, with no window to average (DESIGN §8)")
 AVGPOOL_RULE_NTK = ("ntk: the neural tangent kernel of a model with an AvgPool2d is not "
                     "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
+CORRCONV_RULE_GLOBAL = ("a CorrelatedConv2d downstream of a GlobalAvgPool is not implemented: "
+                        "the value there is 1x1 per pair, with no taps to correlate (DESIGN §8)")
+CORRCONV_RULE_NTK = ("ntk: the neural tangent kernel of a model with a CorrelatedConv2d is not "
+                     "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
 
 
 @dataclasses.dataclass
@@ -434,6 +471,7 @@ class PoolStep:
     fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
     fn "avgpool": dst = mean of src over the windows of p and of q (op.geom)
                                                                          cgp_covmap_avgpool_*
+    fn "corrconv": dst = the correlated-weight conv of src (op.geom)     cgp_corrconv_*
     fn "axpby":   dst = Σ coef·buffer over ``terms`` (coef None: 1)      cgp_axpby_*
     ``free``: the buffers nothing reads after this launch."""
     fn: str
@@ -461,7 +499,8 @@ class PoolSteps:
     final: int
     need_var: frozenset  # values whose per-image variance maps the nonlinearities read
     peak: int           # elements per pair live at the fullest launch
-    # AvgPool2d: the values of the unfused program at or downstream of one, the
+    # AvgPool2d, CorrelatedConv2d: the values of the unfused program at or
+    # downstream of one (either ends the closure of the per-image variances), the
     # values of need_var among them -- their variance maps are the p = q diagonals of the
     # images' self maps, extracted by a pass of steps[:self_last + 1] over the pairs (i, i)
     # (run_self_variances) -- and the index of the step that writes the last of those
@@ -476,7 +515,8 @@ class PoolSteps:
 
 
 def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps:
-    """The launches of a program with a GlobalAvgPool or an AvgPool2d, over the program
+    """The launches of a program with a GlobalAvgPool, an AvgPool2d or a CorrelatedConv2d
+    (which stands where an AvgPool2d may, and marks ``avgpooled`` like one), over the program
     fused with rules 1 and 2 (conv with a ReLU post-stage, a two-term Sum as an addend).
     Values upstream of the GlobalAvgPool are position-pair maps S[p, q]; downstream they are
     1x1 per pair, and only linear ops may follow (they read no variances).  ``body``: the
@@ -487,15 +527,16 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
     variances are the diagonal of the conv's output on the self pairs, which has to exist
     as a map to be read.
 
-    Raises NotImplementedError naming the rule for a ReLU / Erf or an AvgPool2d after a
-    GlobalAvgPool and for a path that does not pass exactly one GlobalAvgPool."""
+    Raises NotImplementedError naming the rule for a ReLU / Erf, an AvgPool2d or a
+    CorrelatedConv2d after a GlobalAvgPool and for a path that does not pass exactly one
+    GlobalAvgPool."""
     pooled = {v0: False}
     avgpooled = {v0: False}
     for op in prog.ops:
         if op.kind == "add":
             avgpooled[op.dst] = any(avgpooled[t] for _, t in op.terms)
         else:
-            avgpooled[op.dst] = op.kind == "avgpool" or avgpooled[op.src]
+            avgpooled[op.dst] = op.kind in ("avgpool", "corrconv") or avgpooled[op.src]
         if op.kind in ("relu", "erf"):
             if pooled[op.src]:
                 raise NotImplementedError(POOL_RULE_NONLIN)
@@ -510,6 +551,10 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
         elif op.kind == "avgpool":
             if pooled[op.src]:
                 raise NotImplementedError(AVGPOOL_RULE_GLOBAL)
+            pooled[op.dst] = False
+        elif op.kind == "corrconv":
+            if pooled[op.src]:
+                raise NotImplementedError(CORRCONV_RULE_GLOBAL)
             pooled[op.dst] = False
         elif op.kind == "conv":
             if pooled[op.src] and tuple(op.shape_out) != (1, 1):
@@ -542,8 +587,8 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
                                   var=op.src, addend=op.addend))
         elif op.kind == "pool":
             steps.append(PoolStep("pool", op.dst, src=op.src, op=op))
-        elif op.kind == "avgpool":
-            steps.append(PoolStep("avgpool", op.dst, src=op.src, op=op))
+        elif op.kind in ("avgpool", "corrconv"):
+            steps.append(PoolStep(op.kind, op.dst, src=op.src, op=op))
         else:
             steps.append(PoolStep("axpby", op.dst, op=op, terms=list(op.terms)))
     last = {}
@@ -604,12 +649,12 @@ class Plan:
         fh, fw = self.prog.shapes[self.vf]
         self.final_hw = (fh, fw)
         self.moments_fused = any(o.pre == N.CGP_PRE_MOMENTS for o in self.pair_ops)
-        # a model with a GlobalAvgPool or an AvgPool2d runs on position-pair maps
-        # (run_pairs_pool); its rejections are raised here, when the program is compiled.
-        # With an AvgPool2d and no GlobalAvgPool the final value is a map (1x1 for forward)
+        # a model with a GlobalAvgPool, an AvgPool2d or a CorrelatedConv2d runs on
+        # position-pair maps (run_pairs_pool); its rejections are raised here, when the program
+        # is compiled.  Without a GlobalAvgPool the final value is a map (1x1 for forward)
         kinds = {o.kind for o in self.prog.ops}
         self.pool = pool_steps(self.prog, self.v0, self.vf, body="pool" not in kinds) \
-            if kinds & {"pool", "avgpool"} else None
+            if kinds & {"pool", "avgpool", "corrconv"} else None
 
     # -- helpers -----------------------------------------------------------------------
     @staticmethod
@@ -648,7 +693,8 @@ class Plan:
         for idx, op in enumerate(ops):
             if op.dst in pooled:
                 # at or after a GlobalAvgPool: linear ops, no variances read; at or after an
-                # AvgPool2d: the recursion is not closed, run_self_variances has them
+                # AvgPool2d or a CorrelatedConv2d: the recursion is not closed,
+                # run_self_variances has them
                 continue
             ho, wo = op.shape_out
             if op.kind == "conv":
@@ -1053,6 +1099,20 @@ class Plan:
             self._body_steps = pool_steps(self.prog, self.v0, self.vf, body=True)
         return self._body_steps
 
+    def _corr_tables(self, op, dev, dtype):
+        """The two tap correlation matrices of a corrconv op on ``dev`` in ``dtype``, uploaded
+        once per plan, device and dtype.  The copy is synchronous: the tables are shared by
+        every stream that runs the plan, and none may see a copy in flight."""
+        cache = self.__dict__.setdefault("_corr_tabs", {})
+        key = (op.dst, str(dev), dtype)
+        tabs = cache.get(key)
+        if tabs is None:
+            tabs = tuple(torch.tensor(m, dtype=torch.float64).to(dtype).to(dev).contiguous()
+                         for m in (op.geom.corr_rows, op.geom.corr_cols))
+            torch.cuda.synchronize(dev)
+            cache[key] = tabs
+        return tabs
+
     def run_self_variances(self, x, var, stream, ps=None, max_bytes=None, want=None):
         """The variance maps [n, h, w] of the values ``want`` (default ps.self_var: what the
         nonlinearities downstream of an AvgPool2d read) of the images x: the p = q diagonals
@@ -1166,6 +1226,16 @@ class Plan:
                     r.k, r.stride = st.op.geom.taps, st.op.geom.stride
                     N.check(getattr(lib, f"cgp_covmap_avgpool_{sfx}")(r, stream),
                             "cgp_covmap_avgpool")
+                elif st.fn == "corrconv":
+                    g = st.op.geom
+                    rr, rc = self._corr_tables(st.op, dev, x.dtype)
+                    r = N.CorrConvArgs()
+                    r.in_, r.out, r.npairs = N.ptr(bufs[st.src]), N.ptr(dst), n
+                    r.corr_rows, r.corr_cols = N.ptr(rr), N.ptr(rc)
+                    (r.h, r.w), r.ho, r.wo = ps.shapes[st.src], h, w
+                    r.taps, r.offset, r.stride, r.dilation = g.taps, g.offset, g.stride, g.dilation
+                    r.weight, r.bias = g.weight, g.bias
+                    N.check(getattr(lib, f"cgp_corrconv_{sfx}")(r, stream), "cgp_corrconv")
                 elif st.fn == "axpby":
                     for k, (coef, b) in enumerate(st.terms):
                         c = 1.0 if coef is None else coef

@@ -386,6 +386,40 @@ int cgp_covmap_diag_f64(const double* in, const int32_t* pair_i, int64_t npairs,
                         int32_t w, double* out, void* stream);
 int cgp_covmap_diag_f32(const float* in, const int32_t* pair_i, int64_t npairs, int32_t h,
                         int32_t w, float* out, void* stream);
+/*
+ * A conv or readout with correlated weights on position-pair maps (additions to ABI 12: no
+ * struct or existing entry point changed).  Taps δ and δ' of one filter have
+ * the correlation R[δ, δ'], separable into rows and columns, so p and q move by different
+ * taps:
+ *   out[m][P][Q][U][V] = weight · Σ_{a,a'<taps} Rr[a][a'] · Σ_{b,b'<taps} Rc[b][b'] ·
+ *                        in[m][P·s+off+a·d][Q·s+off+a'·d][U·s+off+b·d][V·s+off+b'·d] + bias
+ * with a term zero where an index leaves the map.  Rr = Rc = I is cgp_cov_conv_*'s stencil,
+ * all-ones cgp_covmap_avgpool_*'s window sum (times k⁴).  Both tables must be symmetric; the
+ * entries [a][a'] with a <= a' are the ones read.  The row sum is taken first, then the
+ * column sum, all in the map's type, then weight and bias once.  Both sums run over the
+ * offset pairs a <= a' in row-major order and take an offset pair with its mirror first,
+ * Rr[a][a']·(t(a, a') + t(a', a)), so a map that is symmetric bit for bit under p <-> q (a
+ * self pair's) stays so.  The order depends on the geometry alone, not on the grid, the pair
+ * count or how the caller chunks the pairs (several lanes may share one output's column sum:
+ * they take the offset pairs of the list round robin and add their parts in a fixed tree).
+ * A row-offset pair whose Rr entry is exactly zero is not fetched: Rr = I costs taps block
+ * loads per output row pair, a band of half-width c (2c + 1)·taps.  out must not be in.
+ * ho, wo: every output row and column must have a tap inside the map.  One workgroup holds
+ * a w×w block of sums and both tables: they must fit 64 KB of LDS.
+ */
+typedef struct cgp_corrconv_args {
+    const void* in;          /* [npairs][h][h][w][w] */
+    void* out;               /* [npairs][ho][ho][wo][wo] */
+    const void* corr_rows;   /* device [taps][taps], the maps' type */
+    const void* corr_cols;   /* device [taps][taps], the maps' type */
+    int64_t npairs;
+    int32_t h, w, ho, wo;
+    int32_t taps, offset, stride, dilation;   /* as cgp_cov_conv_args */
+    double weight, bias;     /* var_weight/k² and var_bias */
+} cgp_corrconv_args;
+size_t cgp_corrconv_args_size(void);
+int cgp_corrconv_f64(const cgp_corrconv_args* args, void* stream);
+int cgp_corrconv_f32(const cgp_corrconv_args* args, void* stream);
 
 /*
  * out = alpha·a + beta·b (b may be NULL: out = alpha·a), n elements.  The unfused form
