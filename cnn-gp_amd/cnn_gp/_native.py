@@ -123,6 +123,21 @@ class CorrConvArgs(ctypes.Structure):
     ]
 
 
+class GeluArgs(ctypes.Structure):
+    """Mirror of cgp_gelu_args (include/cnngp.h): cgp_erf_args' fields."""
+    _fields_ = list(ErfArgs._fields_)
+
+
+class GeluCovArgs(ctypes.Structure):
+    """Mirror of cgp_gelu_cov_args (include/cnngp.h): cgp_cov_nonlin_args' without kind."""
+    _fields_ = [
+        ("in_", _vp), ("out", _vp), ("addend", _vp), ("xx", _vp), ("yy", _vp),
+        ("pair_i", _vp), ("pair_j", _vp),
+        ("npairs", _i64),
+        ("h", _i32), ("w", _i32), ("same", _i32), ("flags", _i32), ("reserved", _i32),
+    ]
+
+
 class NetOp(ctypes.Structure):
     """Mirror of cgp_net_op (include/cnngp.h)."""
     _fields_ = [
@@ -225,6 +240,14 @@ SIGNATURES = {
     "cgp_corrconv_args_size": (ctypes.c_size_t, []),
     "cgp_corrconv_f64": (_i32, [ctypes.POINTER(CorrConvArgs), _vp]),
     "cgp_corrconv_f32": (_i32, [ctypes.POINTER(CorrConvArgs), _vp]),
+    "cgp_gelu_args_size": (ctypes.c_size_t, []),
+    "cgp_gelu_f64": (_i32, [ctypes.POINTER(GeluArgs), _vp]),
+    "cgp_gelu_f32": (_i32, [ctypes.POINTER(GeluArgs), _vp]),
+    "cgp_var_gelu_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "cgp_var_gelu_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "cgp_gelu_cov_args_size": (ctypes.c_size_t, []),
+    "cgp_gelu_cov_f64": (_i32, [ctypes.POINTER(GeluCovArgs), _vp]),
+    "cgp_gelu_cov_f32": (_i32, [ctypes.POINTER(GeluCovArgs), _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_axpby_f32": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_scale_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _f64, _vp]),
@@ -300,6 +323,8 @@ def load():
                 lib.cgp_cov_nonlin_args_size() != ctypes.sizeof(CovNonlinArgs) or \
                 lib.cgp_covmap_avgpool_args_size() != ctypes.sizeof(CovAvgPoolArgs) or \
                 lib.cgp_corrconv_args_size() != ctypes.sizeof(CorrConvArgs) or \
+                lib.cgp_gelu_args_size() != ctypes.sizeof(GeluArgs) or \
+                lib.cgp_gelu_cov_args_size() != ctypes.sizeof(GeluCovArgs) or \
                 lib.cgp_net_op_size() != ctypes.sizeof(NetOp) or \
                 lib.cgp_net_args_size() != ctypes.sizeof(NetArgs) or \
                 lib.cgp_var_op_size() != ctypes.sizeof(VarOp) or \

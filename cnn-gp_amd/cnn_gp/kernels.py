@@ -22,7 +22,7 @@ from .program import Plan
 # (CGP_VAR_CHAIN=0: the layer-by-layer variance pipeline, one launch per op)
 VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
 
-__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "GlobalAvgPool", "AvgPool2d",
+__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "Gelu", "GlobalAvgPool", "AvgPool2d",
            "CorrelatedConv2d", "rbf_corr", "band_corr", "Sequential", "Mixture", "Sum",
            "resnet_block")
 
@@ -189,8 +189,8 @@ class NNGPKernel(nn.Module):
     def set_exact_relu(self, enabled: bool):
         """Evaluate the ReLU map op by op exactly like the reference (correctly rounded
         1/sqrt, sqrt, acos, division) instead of the closed form (default; within 1e-14 of
-        the exact map, see csrc/relu_poly.h).  For parity studies; ~2x slower.  An Erf has
-        one evaluation mode and ignores it."""
+        the exact map, see csrc/relu_poly.h).  For parity studies; ~2x slower.  An Erf and
+        a Gelu have one evaluation mode and ignore it."""
         for m in self.modules():
             m.__dict__["_cgp_exact_relu"] = bool(enabled)
         return self
@@ -272,6 +272,10 @@ class NNGPKernel(nn.Module):
             Erf             K' = (2/π)·atan(2c/√D),  Θ' = Θ·κ̇,  κ̇ = (4/π)/√D with
                             D = 1 + 2(v₁ + v₂) + 4(v₁v₂ − c²), raised to 1 below 1;
                             κ̇ = (4/π)/√(1 + 4v) where K' is overridden  
+            Gelu            K' as forward,         Θ' = Θ·κ̇,  κ̇ = E[φ'(u₁)φ'(u₂)] =
+                            (1/Δ² + (1 − v₁v₂)/((1 + v₁)(1 + v₂)) + 1)·t/2π + 1/4 + atan(t)/2π,
+                            t = c/Δ, Δ² = (1 + v₁)(1 + v₂) − c² raised to 1 below 1; the same
+                            at c = v₁ = v₂ = v where K' is overridden  
             Sum / Mixture   the same (weighted) sum on both
 
         and the result is Θ of the final 1x1 value; a model without a Conv2d gives zeros
@@ -616,6 +620,19 @@ class Erf(NNGPKernel):
     Williams 1997): K' = (2/π)·asin(2c/√((1+2v₁)(1+2v₂))), evaluated in the atan form of
     DESIGN §3.2 (device: erf_pair).  Runs on the layer path; set_exact_relu has no effect
     on it."""
+
+    def layers(self):
+        return 0
+
+
+class Gelu(NNGPKernel):
+    """The GELU nonlinearity φ(x) = x·Φ(x), the exact one and not its tanh approximation (no
+    reference counterpart; closed form of Tsuchida, Pearce et al. 2021).  With
+    Δ² = (1 + v₁)(1 + v₂) − c² and t = c/Δ:
+    K' = ((c² + v₁v₂·Δ²)/((1 + v₁)(1 + v₂)·Δ) + c·atan(t))/2π + c/4  (device:
+    gelu_map).  Usable wherever Erf is: forward, ntk, position_covariance and the pooled
+    path; a model with one runs on the layer path, and set_exact_relu has no effect on it.
+    The map is not homogeneous (the scale of the inputs matters) and K' can be negative."""
 
     def layers(self):
         return 0

@@ -8,6 +8,7 @@ whole [N1·N2, 1, H, W] covariance tensor.  Here the tree is flattened once into
     v  = conv(u, geometry)           kernels.py:92-98
     v  = relu(u)                     kernels.py:134-165
     v  = erf(u)                      Erf (no reference counterpart)
+    v  = gelu(u)                     Gelu (no reference counterpart)
     v  = add[(coef, u), ...]         Sum (kernels.py:252-254) / Mixture (:220-225)
     v  = pool(u)                     GlobalAvgPool (no reference counterpart; DESIGN §3.3:
                                      such a program runs on position-pair maps, pool_steps)
@@ -20,11 +21,12 @@ and then split into two device pipelines:
 
 * the VARIANCE pipeline runs every op, unfused, on the per-image maps [xx | yy]
   ((N1 + N2) maps — negligible next to the N1·N2 pair maps) and keeps the variances
-  of every value a ReLU or Erf consumes;
+  of every value a ReLU, Erf or Gelu consumes;
 * the PAIR pipeline runs on the N1·N2 maps with ops fused so each HBM pass does the
   most work:  [ReLU|moments] → Conv → [ReLU] → [+ addend]  is ONE kernel
   (cgp_conv_*), a ReLU not adjacent to a single-use conv is cgp_relu_* (+ addend),
-  an Erf is always its own pass cgp_erf_* (+ addend), and only sums that cannot be
+  an Erf or a Gelu is always its own pass cgp_erf_* / cgp_gelu_* (+ addend), and only sums
+  that cannot be
   folded into their producer run as cgp_axpby_*.
 
 Fusion changes no arithmetic: each fused stage performs exactly the operations of the
@@ -71,7 +73,7 @@ class CorrGeom(ConvGeom):
 
 @dataclasses.dataclass
 class Op:
-    # 'conv' | 'relu' | 'erf' | 'add' | 'pool' | 'avgpool' | 'corrconv' | 'moments'
+    # 'conv' | 'relu' | 'erf' | 'gelu' | 'add' | 'pool' | 'avgpool' | 'corrconv' | 'moments'
     kind: str
     dst: int
     src: Optional[int] = None
@@ -189,6 +191,11 @@ def _emit(prog: Program, mod, v: int) -> int:
         prog.ops.append(Op("erf", out, src=v, shape_in=prog.shapes[v],
                            shape_out=prog.shapes[v]))
         return out
+    if isinstance(mod, K.Gelu):
+        out = prog.new_value(prog.shapes[v])
+        prog.ops.append(Op("gelu", out, src=v, shape_in=prog.shapes[v],
+                           shape_out=prog.shapes[v]))
+        return out
     if isinstance(mod, K.GlobalAvgPool):
         out = prog.new_value((1, 1))
         prog.ops.append(Op("pool", out, src=v, shape_in=prog.shapes[v], shape_out=(1, 1)))
@@ -253,9 +260,9 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
          fold_moments: bool = True) -> list:
     """Return the fused op list for the pair pipeline (prog.ops is left untouched).
     ``pre_relu`` / ``fold_moments`` enable rules 3 / 4 (the whole-network kernel keeps
-    standalone ReLU and moments ops: in LDS they cost no extra memory pass).  An erf op is
-    never a conv's pre- or post-stage (rules 1 and 3 match ReLU only); rule 2 may give it an
-    addend."""
+    standalone ReLU and moments ops: in LDS they cost no extra memory pass).  An erf or gelu
+    op is never a conv's pre- or post-stage (rules 1 and 3 match ReLU only); rule 2 may give
+    it an addend."""
     ops = [dataclasses.replace(o, terms=list(o.terms)) for o in prog.ops]
     if not enable:
         return ops
@@ -291,7 +298,7 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
             (_, t0), (_, t1) = a.terms
             for cand, other in ((t1, t0), (t0, t1)):
                 pi = producer(ops, cand)
-                if pi is None or ops[pi].kind not in ("conv", "relu", "erf") or \
+                if pi is None or ops[pi].kind not in ("conv", "relu", "erf", "gelu") or \
                         ops[pi].addend is not None or uses.get(cand, 0) != 1:
                     continue
                 oi = producer(ops, other)
@@ -340,7 +347,7 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
 def needed_variances(ops) -> set:
     need = set()
     for o in ops:
-        if o.kind in ("relu", "erf"):
+        if o.kind in ("relu", "erf", "gelu"):
             need.add(o.src)
         if o.pre == N.CGP_PRE_RELU:
             need.add(o.pre_var)
@@ -363,6 +370,8 @@ class NtkStep:
     fn "relu_ntk": dst, dst_theta = relu(src), theta·κ̇                   cgp_relu_ntk_*
     fn "erf":      dst = erf(src), variances of value ``var``            cgp_erf_* (theta NULL)
     fn "erf_ntk":  dst, dst_theta = erf(src), theta·κ̇                    cgp_erf_*
+    fn "gelu":     dst = gelu(src), variances of value ``var``           cgp_gelu_* (theta NULL)
+    fn "gelu_ntk": dst, dst_theta = gelu(src), theta·κ̇                   cgp_gelu_*
     fn "axpby":    dst = Σ coef·buffer over ``terms`` (coef None: 1)     cgp_axpby_*
     """
     fn: str
@@ -396,11 +405,12 @@ def ntk_steps(prog: Program, v0: int, vf: int):
         ReLU            K' = relu(K),          Θ' = Θ·κ̇,  κ̇ = (π - θ)/2π  (1/2 where the
                         reference overrides K': same and i = j, or same and diag)
         Erf             K' = erf(K),           Θ' = Θ·κ̇,  κ̇ = (4/π)/√D  
+        Gelu            K' = gelu(K),          Θ' = Θ·κ̇,  κ̇ = E[φ'φ']   
         Sum / Mixture   the same (weighted) sum on both streams
 
     A zero Θ is carried as None and costs nothing: the first conv's Θ' IS its K' (the same
-    buffer), a ReLU / Erf on a value with Θ = 0 is the plain cgp_relu_* / forward-only
-    cgp_erf_*, sums skip zero terms
+    buffer), a ReLU / Erf / Gelu on a value with Θ = 0 is the plain cgp_relu_* / forward-only
+    cgp_erf_* / cgp_gelu_*, sums skip zero terms
     (a sum whose only non-zero term has weight 1 passes that term's buffer on)."""
     steps = []
     theta = {v0: None}
@@ -414,7 +424,7 @@ def ntk_steps(prog: Program, v0: int, vf: int):
                 steps.append(NtkStep("conv", ("T", d), src=theta[op.src], op=op, bias=0.0,
                                      addend=("K", d)))
                 theta[d] = ("T", d)
-        elif op.kind in ("relu", "erf"):
+        elif op.kind in ("relu", "erf", "gelu"):
             if theta[op.src] is None:
                 steps.append(NtkStep(op.kind, ("K", d), src=("K", op.src), op=op, var=op.src))
                 theta[d] = None
@@ -455,6 +465,8 @@ AVGPOOL_RULE_NTK = ("ntk: the neural tangent kernel of a model with an AvgPool2d
                     "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
 CORRCONV_RULE_GLOBAL = ("a CorrelatedConv2d downstream of a GlobalAvgPool is not implemented: "
                         "the value there is 1x1 per pair, with no taps to correlate (DESIGN §8)")
+GELU_RULE_GLOBAL = ("a Gelu downstream of a GlobalAvgPool is not implemented: it would need "
+                    "the pooled self-covariances of each image (DESIGN §8)")
 CORRCONV_RULE_NTK = ("ntk: the neural tangent kernel of a model with a CorrelatedConv2d is not "
                      "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
 
@@ -468,6 +480,8 @@ class PoolStep:
                   [+ addend]                                             cgp_cov_conv_*
     fn "nonlin":  dst = relu / erf (``post``) of src, variances of value ``var``
                   [+ addend]                                             cgp_cov_nonlin_*
+    fn "gelu":    dst = gelu of src, variances of value ``var`` [+ addend]
+                                                                         cgp_gelu_cov_*
     fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
     fn "avgpool": dst = mean of src over the windows of p and of q (op.geom)
                                                                          cgp_covmap_avgpool_*
@@ -527,7 +541,7 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
     variances are the diagonal of the conv's output on the self pairs, which has to exist
     as a map to be read.
 
-    Raises NotImplementedError naming the rule for a ReLU / Erf, an AvgPool2d or a
+    Raises NotImplementedError naming the rule for a ReLU / Erf, a Gelu, an AvgPool2d or a
     CorrelatedConv2d after a GlobalAvgPool and for a path that does not pass exactly one
     GlobalAvgPool."""
     pooled = {v0: False}
@@ -540,6 +554,10 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
         if op.kind in ("relu", "erf"):
             if pooled[op.src]:
                 raise NotImplementedError(POOL_RULE_NONLIN)
+            pooled[op.dst] = False
+        elif op.kind == "gelu":
+            if pooled[op.src]:
+                raise NotImplementedError(GELU_RULE_GLOBAL)
             pooled[op.dst] = False
         elif op.kind == "pool":
             if body:
@@ -585,6 +603,9 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
             steps.append(PoolStep("nonlin", op.dst, src=op.src, op=op,
                                   post=N.CGP_COV_RELU if op.kind == "relu" else N.CGP_COV_ERF,
                                   var=op.src, addend=op.addend))
+        elif op.kind == "gelu":
+            steps.append(PoolStep("gelu", op.dst, src=op.src, op=op, var=op.src,
+                                  addend=op.addend))
         elif op.kind == "pool":
             steps.append(PoolStep("pool", op.dst, src=op.src, op=op))
         elif op.kind in ("avgpool", "corrconv"):
@@ -678,7 +699,7 @@ class Plan:
 
     # -- variance pipeline --------------------------------------------------------------
     def run_variances(self, xx0, yy0, n1, n2, same, stream, need=None):
-        """Per-image variance maps of every value a ReLU or Erf reads (or of ``need``).
+        """Per-image variance maps of every value a ReLU, Erf or Gelu reads (or of ``need``).
         xx0/yy0: [n, H, W]."""
         sfx = self._sfx(xx0.dtype)
         dev = xx0.device
@@ -716,7 +737,7 @@ class Plan:
                     a.weight, a.bias = g.weight, g.bias
                     N.check(getattr(N.load(), f"cgp_conv_{sfx}")(a, stream), "cgp_conv")
                 out = (buf[:n1], buf[n1:])
-            elif op.kind in ("relu", "erf"):
+            elif op.kind in ("relu", "erf", "gelu"):
                 xin, yin = vals[op.src]
                 buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
                 N.call(f"cgp_var_{op.kind}_{sfx}", N.ptr(xin), N.ptr(yin), n1, n2, ho * wo,
@@ -756,7 +777,7 @@ class Plan:
         """cgp_var_op records of the variance program (cached per need/quarter/device):
         LDS slots by first fit over the values' live ranges, store offsets per image.
         None when the program has an op the chain kernel lacks (a Sum of > 4 terms, an
-        Erf)."""
+        Erf, a Gelu)."""
         key = (frozenset(need), frozenset(quarter), str(dev))
         cache = self.__dict__.setdefault("_var_chains", {})
         if key in cache:
@@ -953,17 +974,18 @@ class Plan:
                 r.flags = self.flags
                 fn = getattr(lib, f"cgp_relu_{sfx}")
                 launch = (lambda fn=fn, r=r: N.check(fn(r, stream), "cgp_relu"))
-            elif op.kind == "erf":
+            elif op.kind in ("erf", "gelu"):
                 out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
                 vx, vy = var[op.src]
-                r = N.ErfArgs()
+                r = N.ErfArgs() if op.kind == "erf" else N.GeluArgs()
                 r.xy, r.out_xy = N.ptr(vals[op.src]), N.ptr(out)
                 r.addend = N.ptr(vals[op.addend]) if op.addend is not None else None
                 r.xx, r.yy = N.ptr(vx), N.ptr(vy)
                 r.nmaps, r.n1, r.n2 = nmaps, n1, n2
                 r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
-                fn = getattr(lib, f"cgp_erf_{sfx}")
-                launch = (lambda fn=fn, r=r: N.check(fn(r, stream), "cgp_erf"))
+                fn = getattr(lib, f"cgp_{op.kind}_{sfx}")
+                launch = (lambda fn=fn, r=r, what="cgp_" + op.kind:
+                          N.check(fn(r, stream), what))
             elif op.kind == "add":
                 out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
                 n = nmaps * ho * wo
@@ -990,9 +1012,9 @@ class Plan:
 
     # -- NTK: K and Θ through the unfused program ------------------------------------------
     def ntk_need_var(self) -> set:
-        """The values whose variance maps the NTK run reads: every ReLU's and Erf's source
-        in the unfused program (run_variances(need=...))."""
-        return {o.src for o in self.prog.ops if o.kind in ("relu", "erf")}
+        """The values whose variance maps the NTK run reads: every ReLU's, Erf's and Gelu's
+        source in the unfused program (run_variances(need=...))."""
+        return {o.src for o in self.prog.ops if o.kind in ("relu", "erf", "gelu")}
 
     def run_pairs_ntk(self, xy0, var, n1, n2, same, diag, stream):
         """Runs ntk_steps on the pair maps; returns (K, Θ) of the final value as
@@ -1001,7 +1023,8 @@ class Plan:
         maps of ntk_need_var().
 
         Buffers are freed after their last reader, as in run_pairs.  Peak live pair maps:
-        4 on a Conv2d/ReLU chain (K, Θ and K', Θ' of a cgp_relu_ntk_* or cgp_erf_* step;
+        4 on a Conv2d/ReLU chain (K, Θ and K', Θ' of a cgp_relu_ntk_*, cgp_erf_* or cgp_gelu_*
+        step;
         3 at a conv's Θ launch), plus 2 (K and Θ) for every Sum / Mixture branch result or skip value
         waiting for its sum -- 6 inside a residual block of the ResNets."""
         sfx = self._sfx(xy0.dtype)
@@ -1062,18 +1085,18 @@ class Plan:
                 r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
                 r.flags = self.flags
                 N.check(getattr(lib, f"cgp_relu_ntk_{sfx}")(r, stream), "cgp_relu_ntk")
-            elif st.fn in ("erf", "erf_ntk"):
+            elif st.fn in ("erf", "erf_ntk", "gelu", "gelu_ntk"):
                 out = bufs[st.dst] = new(op)
                 vx, vy = var[st.var]
-                r = N.ErfArgs()
+                r = N.ErfArgs() if op.kind == "erf" else N.GeluArgs()
                 r.xy, r.out_xy = N.ptr(bufs[st.src]), N.ptr(out)
-                if st.fn == "erf_ntk":
+                if st.fn.endswith("_ntk"):
                     tout = bufs[st.dst_theta] = new(op)
                     r.theta, r.out_theta = N.ptr(bufs[st.theta]), N.ptr(tout)
                 r.xx, r.yy = N.ptr(vx), N.ptr(vy)
                 r.nmaps, r.n1, r.n2 = nmaps, n1, n2
                 r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
-                N.check(getattr(lib, f"cgp_erf_{sfx}")(r, stream), "cgp_erf")
+                N.check(getattr(lib, f"cgp_{op.kind}_{sfx}")(r, stream), "cgp_" + op.kind)
             elif st.fn == "axpby":
                 out = bufs[st.dst] = new(op)
                 n = nmaps * ho * wo
@@ -1215,6 +1238,15 @@ class Plan:
                     r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
                     r.h, r.w, r.kind, r.same, r.flags = h, w, st.post, int(same), self.flags
                     N.check(getattr(lib, f"cgp_cov_nonlin_{sfx}")(r, stream), "cgp_cov_nonlin")
+                elif st.fn == "gelu":
+                    vx, vy = var[st.var]
+                    r = N.GeluCovArgs()
+                    r.in_, r.out = N.ptr(bufs[st.src]), N.ptr(dst)
+                    r.addend = N.ptr(bufs[st.addend]) if st.addend is not None else None
+                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
+                    r.h, r.w, r.same = h, w, int(same)
+                    N.check(getattr(lib, f"cgp_gelu_cov_{sfx}")(r, stream), "cgp_gelu_cov")
                 elif st.fn == "pool":
                     N.check(getattr(lib, f"cgp_cov_pool_{sfx}")(
                         N.ptr(bufs[st.src]), n, ps.elems(st.src), N.ptr(dst), stream),

@@ -422,6 +422,77 @@ int cgp_corrconv_f64(const cgp_corrconv_args* args, void* stream);
 int cgp_corrconv_f32(const cgp_corrconv_args* args, void* stream);
 
 /*
+ * The GELU nonlinearity φ(x) = x·Φ(x) (additions to ABI 12: no struct or existing entry
+ * point changed; no reference counterpart).  The exact GELU, not its tanh
+ * approximation.  Its layer kernel in closed form (Tsuchida, Pearce et al. 2021, "Avoiding
+ * kernel fixed points: computing with ELU and GELU infinite networks"), in the conventions
+ * of the ReLU and erf entry points above -- per pixel (xy, xx, yy) = (c, v1, v2), no
+ * rescaling.  With P = v1·v2, P1 = (1 + v1)(1 + v2), Δ² = P1 - c², raised to 1 where it
+ * falls below 1 (NaN kept; Δ² >= 1 + v1 + v2 for a valid covariance, so there is no
+ * singularity at ρ = ±1), Δ = √Δ², t = c/Δ and a = atan(t):
+ *   pair map    out_xy = ((c² + P·Δ²)/(P1·Δ) + c·a)/(2π) + c/4
+ *   variances   s = √(1 + 2v): v' = (2v²/((1 + v)·s) + v·atan(v/s))/(2π) + v/4, the pair
+ *               map at c = v1 = v2 = v
+ *   NTK         out_theta = theta·κ̇,  κ̇ = (1/Δ² + (1 - P)/P1 + 1)·t/(2π) + 1/4 + a/(2π)
+ *               = ∂out_xy/∂c at fixed variances = E[φ'(u1)·φ'(u2)]
+ * Where cgp_relu_* overrides its map (same && !diag: pairs i == j; same && diag: all),
+ * out_xy = v'[i], the same bits cgp_var_gelu_* writes, and κ̇ is the NTK line at
+ * c = v1 = v2 = v: (1/(1 + 2v) + (1 - v)/(1 + v) + 1)·(v/s)/(2π) + 1/4 + atan(v/s)/(2π).
+ * A zero variance needs no guard (c = v = 0: out_xy = 0, κ̇ = 1/4).  out_xy can be negative,
+ * and the map is not homogeneous: the input scale matters.  One evaluation mode: division
+ * and square root correctly rounded, atan from the device math library, every op rounded in
+ * the map's type (the /(2π) above is a product with the constant 1/(2π)); flags is ignored.
+ *
+ * cgp_gelu_args has the fields and the rules of cgp_erf_args: theta == NULL is the
+ * forward-only pass; in-place (out_xy == xy, out_theta == theta) is allowed, and theta may
+ * be xy itself; addend (optional) is added to out_xy only, as a separate rounding; same or
+ * diag need n1 == n2; hw is at most 2048; nmaps < 2^31.
+ */
+typedef struct cgp_gelu_args {
+    const void* xy;         /* [nmaps][hw] */
+    const void* theta;      /* [nmaps][hw] or NULL */
+    void* out_xy;           /* [nmaps][hw] */
+    void* out_theta;        /* [nmaps][hw] (unused when theta is NULL) */
+    const void* addend;     /* [nmaps][hw] or NULL */
+    const void* xx;         /* [n1][hw] variances at the GELU input */
+    const void* yy;         /* [n2][hw] (may be NULL when same && diag) */
+    int64_t nmaps, n1, n2;
+    int32_t hw, same, diag, flags;
+} cgp_gelu_args;
+size_t cgp_gelu_args_size(void);
+int cgp_gelu_f64(const cgp_gelu_args* args, void* stream);
+int cgp_gelu_f32(const cgp_gelu_args* args, void* stream);
+/* GELU on the per-image variances: xx' = v'(xx); yy' = xx' if same else v'(yy).
+ * xx: [n1][hw], yy: [n2][hw]. */
+int cgp_var_gelu_f64(const double* xx, const double* yy, int64_t n1, int64_t n2, int32_t hw,
+                     int32_t same, double* xx_out, double* yy_out, void* stream);
+int cgp_var_gelu_f32(const float* xx, const float* yy, int64_t n1, int64_t n2, int32_t hw,
+                     int32_t same, float* xx_out, float* yy_out, void* stream);
+/*
+ * GELU on position-pair maps, out = map(in) [+ addend], with cgp_cov_nonlin_*'s element
+ * rule: (c, v1, v2) = (in[m][p, q], xx[pair_i[m]][p], yy[pair_j[m]][q]), and the override
+ * (out = v'[pair_i[m]][p]) where same, pair_i[m] == pair_j[m] and p == q.  In-place
+ * (out == in) is allowed: every element is read and written by one thread.
+ */
+typedef struct cgp_gelu_cov_args {
+    const void* in;          /* [npairs][h][h][w][w] */
+    void* out;
+    const void* addend;      /* like out, or NULL */
+    const void* xx;          /* [n1][h][w] variances at the GELU input */
+    const void* yy;          /* [n2][h][w] (same: may be xx) */
+    const int32_t* pair_i;   /* device [npairs] */
+    const int32_t* pair_j;
+    int64_t npairs;
+    int32_t h, w;
+    int32_t same;
+    int32_t flags;           /* ignored */
+    int32_t reserved;
+} cgp_gelu_cov_args;
+size_t cgp_gelu_cov_args_size(void);
+int cgp_gelu_cov_f64(const cgp_gelu_cov_args* args, void* stream);
+int cgp_gelu_cov_f32(const cgp_gelu_cov_args* args, void* stream);
+
+/*
  * out = alpha·a + beta·b (b may be NULL: out = alpha·a), n elements.  The unfused form
  * of Sum (alpha = beta = 1, kernel_patch.py:43-63) and Mixture (kernels.py:220-225).
  * Products and the sum are rounded separately (no FMA contraction), like torch.
