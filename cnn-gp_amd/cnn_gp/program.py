@@ -777,7 +777,9 @@ class Plan:
         """cgp_var_op records of the variance program (cached per need/quarter/device):
         LDS slots by first fit over the values' live ranges, store offsets per image.
         None when the program has an op the chain kernel lacks (a Sum of > 4 terms, an
-        Erf, a Gelu)."""
+        Erf, a Gelu).  The records are uploaded once per plan, need set and device, and the
+        copy is synchronous (on the uploading stream alone, not the device): the records are
+        shared by every stream that runs the plan, and none may see a copy in flight."""
         key = (frozenset(need), frozenset(quarter), str(dev))
         cache = self.__dict__.setdefault("_var_chains", {})
         if key in cache:
@@ -861,8 +863,9 @@ class Plan:
         hs = max([r.h * r.wo for r in recs if r.kind == N.CGP_VAR_CONV] + [2])
         top[0] += hs + (hs & 1)
         arr = (N.VarOp * len(recs))(*recs)
-        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).pin_memory()
-        chain = dict(ops=host.to(dev, non_blocking=True), nops=len(recs), lds=top[0],
+        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+        # a blocking copy: it returns once the uploading stream has run it
+        chain = dict(ops=host.to(dev), nops=len(recs), lds=top[0],
                      scratch=scratch,
                      store=store, qstore=qstore, total=total, qtotal=qtotal)
         cache[key] = chain
