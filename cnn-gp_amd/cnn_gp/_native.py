@@ -21,6 +21,7 @@ CGP_FLAG_NET_DUAL = 4
 CGP_PRE_NONE, CGP_PRE_RELU, CGP_PRE_MOMENTS = 0, 1, 2
 CGP_POST_NONE, CGP_POST_RELU = 0, 1
 CGP_COV_NONE, CGP_COV_RELU, CGP_COV_ERF = 0, 1, 2
+CGP_COV_GELU = 3                 # cgp_covntk_nonlin_* / cgp_covntk_conv_* only
 CGP_NET_CONV, CGP_NET_RELU, CGP_NET_MOMENTS, CGP_NET_LINEAR = 0, 1, 2, 3
 CGP_NET_LOAD, CGP_NET_STORE = 4, 5
 CGP_NET_CODE_HS_CLEAN = 0x100
@@ -138,6 +139,32 @@ class GeluCovArgs(ctypes.Structure):
     ]
 
 
+class CovNonlinNtkArgs(ctypes.Structure):
+    """Mirror of cgp_covntk_nonlin_args (include/cnngp.h)."""
+    _fields_ = [
+        ("in_", _vp), ("theta", _vp), ("out", _vp), ("out_theta", _vp),
+        ("addend", _vp), ("addend_theta", _vp), ("xx", _vp), ("yy", _vp),
+        ("pair_i", _vp), ("pair_j", _vp),
+        ("npairs", _i64),
+        ("h", _i32), ("w", _i32), ("kind", _i32), ("same", _i32), ("flags", _i32),
+        ("reserved", _i32),
+    ]
+
+
+class CovConvNtkArgs(ctypes.Structure):
+    """Mirror of cgp_covntk_conv_args (include/cnngp.h)."""
+    _fields_ = [
+        ("in_", _vp), ("theta", _vp), ("out", _vp), ("out_theta", _vp),
+        ("addend", _vp), ("addend_theta", _vp), ("xx", _vp), ("yy", _vp),
+        ("pair_i", _vp), ("pair_j", _vp),
+        ("npairs", _i64),
+        ("h", _i32), ("w", _i32), ("ho", _i32), ("wo", _i32),
+        ("taps", _i32), ("offset", _i32), ("stride", _i32), ("dilation", _i32),
+        ("post", _i32), ("same", _i32), ("flags", _i32), ("reserved", _i32),
+        ("weight", _f64), ("bias", _f64),
+    ]
+
+
 class NetOp(ctypes.Structure):
     """Mirror of cgp_net_op (include/cnngp.h)."""
     _fields_ = [
@@ -248,6 +275,12 @@ SIGNATURES = {
     "cgp_gelu_cov_args_size": (ctypes.c_size_t, []),
     "cgp_gelu_cov_f64": (_i32, [ctypes.POINTER(GeluCovArgs), _vp]),
     "cgp_gelu_cov_f32": (_i32, [ctypes.POINTER(GeluCovArgs), _vp]),
+    "cgp_covntk_nonlin_args_size": (ctypes.c_size_t, []),
+    "cgp_covntk_nonlin_f64": (_i32, [ctypes.POINTER(CovNonlinNtkArgs), _vp]),
+    "cgp_covntk_nonlin_f32": (_i32, [ctypes.POINTER(CovNonlinNtkArgs), _vp]),
+    "cgp_covntk_conv_args_size": (ctypes.c_size_t, []),
+    "cgp_covntk_conv_f64": (_i32, [ctypes.POINTER(CovConvNtkArgs), _vp]),
+    "cgp_covntk_conv_f32": (_i32, [ctypes.POINTER(CovConvNtkArgs), _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_axpby_f32": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_scale_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _f64, _vp]),
@@ -325,6 +358,8 @@ def load():
                 lib.cgp_corrconv_args_size() != ctypes.sizeof(CorrConvArgs) or \
                 lib.cgp_gelu_args_size() != ctypes.sizeof(GeluArgs) or \
                 lib.cgp_gelu_cov_args_size() != ctypes.sizeof(GeluCovArgs) or \
+                lib.cgp_covntk_nonlin_args_size() != ctypes.sizeof(CovNonlinNtkArgs) or \
+                lib.cgp_covntk_conv_args_size() != ctypes.sizeof(CovConvNtkArgs) or \
                 lib.cgp_net_op_size() != ctypes.sizeof(NetOp) or \
                 lib.cgp_net_args_size() != ctypes.sizeof(NetArgs) or \
                 lib.cgp_var_op_size() != ctypes.sizeof(VarOp) or \

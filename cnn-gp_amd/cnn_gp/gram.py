@@ -145,9 +145,10 @@ def model_kern(model, device=None, dtype=None) -> ModelKern:
     return ModelKern(model, device, dtype)
 
 
-def ntk_kern(model, device=None, dtype=None) -> Callable:
+def ntk_kern(model, device=None, dtype=None, maps: bool = False) -> Callable:
     """kern(x, x2, same) -> device tensor: the model's neural tangent kernel
-    (NNGPKernel.ntk) of one tile, for gram_tiles / gram_local / gram_strip /
+    (NNGPKernel.ntk; with ``maps`` NNGPKernel.ntk_maps, Θ carried on position-pair maps: the
+    route of models with a GlobalAvgPool, an AvgPool2d or a CorrelatedConv2d) of one tile, for gram_tiles / gram_local / gram_strip /
     classify_distributed in place of model_kern's.  A plain callable, not a ModelKern: the
     NTK runs layer by layer, so there is no whole-build form to ``bind``.
 
@@ -157,12 +158,13 @@ def ntk_kern(model, device=None, dtype=None) -> Callable:
     def kern(x, x2, same, diag=None):
         dev = _default_device(device)
         xd = x.to(dev, dtype or x.dtype)
+        ntk = model.ntk_maps if maps else model.ntk
         with torch.no_grad():
             if same and not diag:
-                th = model.ntk(xd)
+                th = ntk(xd)
             else:
                 x2d = xd if x2 is x else x2.to(dev, dtype or x2.dtype)
-                th = model.ntk(xd, x2d, bool(same), bool(diag))
+                th = ntk(xd, x2d, bool(same), bool(diag))
         return th if diag is None else th.detach().cpu().numpy()
     return kern
 
@@ -330,12 +332,16 @@ def gather_gram(local: torch.Tensor, N: int, N2: Optional[int], batch_size: int,
 
 
 def gram_matrix(model, X, X2=None, batch_size: int = 1024, device=None,
-                dtype=torch.float64, group=None, split: str = "balanced", ntk: bool = False):
+                dtype=torch.float64, group=None, split: str = "balanced", ntk=False):
     """Full Gram matrix of ``model`` on X (× X2) on the device — single GPU, or sharded
     over the torch.distributed group (one process per GPU: each rank evaluates its tiles
     into a flat buffer, rank 0 gathers them; other ranks return None).  ``ntk``: the
-    neural tangent kernel (ntk_kern) instead of the NNGP kernel."""
-    kern = ntk_kern(model, device) if ntk else model_kern(model, device)
+    neural tangent kernel (ntk_kern) instead of the NNGP kernel; ntk="maps": the neural
+    tangent kernel on position-pair maps (ntk_kern(maps=True): pooled and correlated-weight
+    models)."""
+    if isinstance(ntk, str) and ntk != "maps":
+        raise ValueError(f"gram_matrix: ntk is True, False or 'maps', not {ntk!r}")
+    kern = ntk_kern(model, device, maps=ntk == "maps") if ntk else model_kern(model, device)
     N = len(X)
     N2 = None if X2 is None else len(X2)
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:

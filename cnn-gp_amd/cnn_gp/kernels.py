@@ -21,6 +21,9 @@ from .program import Plan
 # the whole-network path computes the per-image variance maps with one cgp_var_chain launch
 # (CGP_VAR_CHAIN=0: the layer-by-layer variance pipeline, one launch per op)
 VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
+# ntk_maps lowers a conv to the two-stream cgp_covntk_conv_* (DESIGN §3.7 has the measurement
+# behind the default; set_ntk_maps_fusion overrides it per model)
+NTK_MAPS_FUSED = True
 
 __all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "Gelu", "GlobalAvgPool", "AvgPool2d",
            "CorrelatedConv2d", "rbf_corr", "band_corr", "Sequential", "Mixture", "Sum",
@@ -283,8 +286,8 @@ class NNGPKernel(nn.Module):
         Equivalently Θ = Σ over all Conv2d outputs of ⟨∂K_final/∂K_xy^l, K_xy^l⟩ at fixed
         variances.  Always evaluated layer by layer (program.ntk_steps: the whole-network
         kernel carries one map); honours set_exact_relu.  A model with a GlobalAvgPool, an
-        AvgPool2d or a CorrelatedConv2d raises NotImplementedError (Θ on position-pair maps:
-        DESIGN §8)."""
+        AvgPool2d or a CorrelatedConv2d raises NotImplementedError here: its Θ is carried on
+        position-pair maps by ``ntk_maps`` (and ``position_ntk``), DESIGN §3.7."""
         y, same, diag, empty = self._prologue(x, y, same, diag)
         plan = self._plan(x.size(2), x.size(3))
         if plan.pool is not None:
@@ -413,6 +416,14 @@ class NNGPKernel(nn.Module):
         them, the pairs i <= j of a same tile, or (i, i) for diag.  Returns (the final value
         of every pair [npairs, elements], pair_i, pair_j) with the pair lists as int64
         index tensors."""
+        pi, pj, var, ws = self._pool_pairs(plan, ps, x, y, same, diag, stream)
+        r = plan.run_pairs_pool(x, y, var, pi.to(torch.int32), pj.to(torch.int32), same, stream,
+                                ps, ws)
+        return r, pi, pj
+
+    def _pool_pairs(self, plan, ps, x, y, same, diag, stream):
+        """The pair lists of a tile (int64 index tensors), the variance maps ``ps`` reads
+        and the workspace bound: what a run on position-pair maps starts from."""
         n1, c, h, w = x.shape
         n2 = y.shape[0]
         dev = x.device
@@ -441,9 +452,114 @@ class NNGPKernel(nn.Module):
                 plan.run_self_variances(y, {v: m[1] for v, m in var.items()}, stream, ps, ws)
             var = dict(var)
             var.update({v: (sx[v], sy[v]) for v in ps.self_var})
-        r = plan.run_pairs_pool(x, y, var, pi.to(torch.int32), pj.to(torch.int32), same, stream,
-                                ps, ws)
-        return r, pi, pj
+        return pi, pj, var, ws
+
+    # ---- the NTK on position-pair maps ---------------------------------
+    def set_ntk_maps_fusion(self, enabled: bool):
+        """Lower the convs of ntk_maps / position_ntk to the two-stream cgp_covntk_conv_*
+        (default) or to the launch-by-launch sequence; the results are the same bits."""
+        for m in self.modules():
+            m.__dict__["_cgp_ntk_maps_fused"] = bool(enabled)
+        return self
+
+    def _run_pool_ntk(self, plan, body, x, y, same, diag, stream):
+        """(K, Θ, pair_i, pair_j) of the tile's pairs through program.pool_ntk_steps; K and Θ
+        [npairs, elements], Θ zeros for a model without a conv."""
+        ns = plan.pool_ntk(body, getattr(self, "_cgp_ntk_maps_fused", NTK_MAPS_FUSED),
+                           x.element_size())
+        pi, pj, var, ws = self._pool_pairs(plan, ns.forward, x, y, same, diag, stream)
+        k, th = plan.run_pairs_pool_ntk(x, y, var, pi.to(torch.int32), pj.to(torch.int32), same,
+                                        stream, ns, ws)
+        return k, (torch.zeros_like(k) if th is None else th), pi, pj
+
+    def ntk_maps(self, x, y=None, same=None, diag=False, return_nngp=False):
+        """The neural tangent kernel Θ, [N1, N2] (or [N1] when diag), carried on position-pair
+        maps; with ``return_nngp`` the pair (K, Θ).  Valid for every model forward runs on
+        position-pair maps -- a GlobalAvgPool, AvgPool2d or CorrelatedConv2d anywhere the
+        forward rules allow, with ReLU, Erf and Gelu -- and for a model with none of them,
+        where it is a second, slower route to ``ntk``'s result.
+
+        The recursion is ntk's, with the pooling layers the same linear op on both streams
+        and a CorrelatedConv2d the conv's rule with its own stencil:
+
+            Conv2d, CorrelatedConv2d   K' = A(K) + var_bias,  Θ' = A(Θ) + K'
+            ReLU / Erf / Gelu          K' as forward,         Θ' = Θ·κ̇   (ntk's κ̇ of
+                                       (S[p, q], xx_i[p], yy_j[q]); the override's value
+                                       where same, i = j and p = q)
+            AvgPool2d, GlobalAvgPool   the same average of K and of Θ
+            Sum / Mixture              the same (weighted) sum on both
+
+        Arguments, dtypes, devices, the empty-batch result, the "not 1x1" error and the
+        same-tile handling (pairs i <= j, then mirrored: symmetric bit for bit) are
+        forward's; for a model forward itself runs on position-pair maps K is forward's, bit
+        for bit.  Honours set_exact_relu and set_pool_workspace (a chunk holds K and Θ)."""
+        y, same, diag, empty = self._prologue(x, y, same, diag)
+        plan = self._plan(x.size(2), x.size(3))
+        body = not any(o.kind == "pool" for o in plan.prog.ops)
+        plan.pool_ntk(body, True, 8)                  # the lowering's rejections come first
+        if empty is not None:
+            return (empty, empty.clone()) if return_nngp else empty
+        out_device = x.device
+        dev = self._compute_device(x)
+        if plan.final_hw != (1, 1):                              # kernels.py:53-57
+            raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
+                               " per pair, not 1x1: add a final Conv2d covering the map")
+        n1, n2 = len(x), len(y)
+        with torch.no_grad(), torch.cuda.device(dev):
+            xd = _to_device(x, dev)
+            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
+            k, th, pi, pj = self._run_pool_ntk(plan, body, xd, yd, same, diag,
+                                               _stream_handle(dev))
+            outs = []
+            for r in (k, th):
+                if diag:
+                    outs.append(r.view(n1))
+                elif not same:
+                    outs.append(r.view(n1, n2))
+                else:
+                    # the pairs i <= j, mirrored: symmetric bit for bit
+                    full = torch.empty((n1, n1), dtype=x.dtype, device=dev)
+                    full[pj, pi] = r.view(-1)
+                    full[pi, pj] = r.view(-1)
+                    outs.append(full)
+        if out_device != dev:
+            outs = [o.to(out_device) for o in outs]
+        return (outs[0], outs[1]) if return_nngp else outs[1]
+
+    def position_ntk(self, x, y=None, same=None, diag=False, return_nngp=False):
+        """position_covariance's twin for Θ: Θ[i, j, p, q] of a model without a GlobalAvgPool,
+        [N1, N2, H', W', H', W'] (diag: [N1, H', W', H', W']) in the order (p_row, p_col, q_row,
+        q_col) -- what a GlobalAvgPool after this model averages in ntk_maps; on a same tile
+        the pairs i > j are the mirror Θ_ji[q, p] = Θ_ij[p, q].  With ``return_nngp`` the pair
+        (S, Θ), S position_covariance's map."""
+        y, same, diag, empty = self._prologue(x, y, same, diag)
+        plan = self._plan(x.size(2), x.size(3))
+        ho, wo = plan.pool_ntk(True, True, 8).forward.shapes[plan.vf]
+        lead = (len(x),) if diag else (len(x), len(y))
+        if empty is not None:
+            e = torch.empty(lead + (ho, wo, ho, wo), dtype=x.dtype, device=x.device)
+            return (e, e.clone()) if return_nngp else e
+        out_device = x.device
+        dev = self._compute_device(x)
+        with torch.no_grad(), torch.cuda.device(dev):
+            xd = _to_device(x, dev)
+            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
+            k, th, pi, pj = self._run_pool_ntk(plan, True, xd, yd, same, diag,
+                                               _stream_handle(dev))
+            outs = []
+            for r in (k, th):
+                # internal layout [p_row][q_row][p_col][q_col] -> (p_row, p_col, q_row, q_col)
+                r = r.view(-1, ho, ho, wo, wo).permute(0, 1, 3, 2, 4)
+                if same and not diag:
+                    s = torch.empty(lead + (ho, wo, ho, wo), dtype=x.dtype, device=dev)
+                    s[pj, pi] = r.permute(0, 3, 4, 1, 2)         # Θ_ji[q, p] = Θ_ij[p, q]
+                    s[pi, pj] = r
+                else:
+                    s = r.reshape(lead + (ho, wo, ho, wo))
+                outs.append(s)
+        if out_device != dev:
+            outs = [o.to(out_device) for o in outs]
+        return (outs[0], outs[1]) if return_nngp else outs[1]
 
     def position_covariance(self, x, y=None, same=None, diag=False):
         """The position-pair covariance map of the model's output: S[i, j, p, q], the

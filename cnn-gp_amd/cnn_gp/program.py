@@ -637,6 +637,223 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
 
 
 # ------------------------------------------------------------------------------------
+# the neural tangent kernel on position-pair maps
+# ------------------------------------------------------------------------------------
+# csrc/covntk.hip kMaxLds: bytes of LDS a cgp_covntk_conv_* workgroup may take
+COV_NTK_MAX_LDS = 64 * 1024
+
+
+def conv_ntk_fits(taps: int, w: int, streams: int, itemsize: int) -> bool:
+    """cgp_covntk_conv_*'s own check: the ``taps`` w x w blocks of every staged stream and one
+    row pair's index entries fit the LDS cap of a workgroup."""
+    unit = streams * taps * w * w * itemsize + 8 * taps + 12
+    return unit + 8 <= COV_NTK_MAX_LDS and taps <= 1024
+
+
+@dataclasses.dataclass
+class PoolNtkStep:
+    """One launch of a pooled NTK run.  Buffers are named ("K", v) / ("T", v), the K and Θ
+    position-pair maps of an SSA value, as in ntk_steps; v is ("pre", d) for the conv
+    output that a fused addend replaced in the forward program.
+
+    The forward launches of PoolStep, on either stream (fn "moments", "conv", "nonlin", "gelu",
+    "pool", "avgpool", "corrconv", "axpby"; ``bias`` replaces a conv geometry's: 0 on the Θ
+    stream), and
+    fn "conv_ntk":   dst, dst_theta = the two-stream conv of (src, theta), theta None for
+                     Θ = 0, [→ nonlinearity ``post``] [+ addend, + addend_theta]
+                                                                          cgp_covntk_conv_*
+    fn "nonlin_ntk": dst, dst_theta = ``post`` of src [+ addend], theta·κ̇ [+ addend_theta]
+                                                                          cgp_covntk_nonlin_*
+    fn "accum":      dst = dst + src, in place                            cgp_axpby_*
+    ``free``: the buffers nothing reads after this launch."""
+    fn: str
+    dst: tuple
+    src: Optional[tuple] = None
+    op: Optional[Op] = None
+    post: int = N.CGP_COV_NONE
+    var: Optional[int] = None
+    addend: Optional[tuple] = None
+    bias: Optional[float] = None
+    theta: Optional[tuple] = None
+    dst_theta: Optional[tuple] = None
+    addend_theta: Optional[tuple] = None
+    terms: list = dataclasses.field(default_factory=list)
+    free: list = dataclasses.field(default_factory=list)
+
+    def reads(self):
+        r = [b for b in (self.src, self.addend, self.theta, self.addend_theta)
+             if b is not None]
+        if self.fn == "accum":
+            r.append(self.dst)
+        return r + [b for _, b in self.terms]
+
+    def writes(self):
+        return [b for b in (self.dst, self.dst_theta) if b is not None]
+
+
+@dataclasses.dataclass
+class PoolNtkSteps:
+    """pool_ntk_steps' result: PoolSteps' fields over the buffers of both streams, plus
+    ``final_theta`` (the buffer that holds Θ of the final value: ``final`` itself after a
+    single conv, None for Θ = 0) and ``forward``, the forward-only PoolSteps of the same
+    program (its self pass gives the variances downstream of an AvgPool2d)."""
+    steps: list
+    shapes: dict
+    maps: frozenset
+    scalars: frozenset
+    final: tuple
+    final_theta: Optional[tuple]
+    need_var: frozenset
+    peak: int
+    forward: PoolSteps
+    fused: bool = True
+
+    def elems(self, b) -> int:
+        h, w = self.shapes[b]
+        return (h * w) ** 2 if b in self.maps else 1
+
+
+def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: bool = True,
+                   itemsize: int = 8) -> PoolNtkSteps:
+    """The launches that carry (K, Θ) through a program on position-pair maps: the two-stream
+    counterpart of pool_steps, over the same fused program and with the same rejections.
+
+    The recursion, with Θ = 0 at the input moments and A a conv's stencil without the bias:
+
+        Conv2d, CorrelatedConv2d   K' = A(K) + b,   Θ' = A(Θ) + K'   (correlated weights are a
+                                   fixed linear map of i.i.d. parameters: the conv's rule, A_R)
+        ReLU / Erf / Gelu          K' as forward,   Θ' = Θ·κ̇
+        AvgPool2d, GlobalAvgPool   the same linear op on both
+        Sum / Mixture              the same (weighted) sum on both
+
+    A zero Θ is carried as None and costs nothing, as in ntk_steps: the first conv's Θ' is its
+    K' buffer, a nonlinearity on Θ = None is the forward-only launch, sums skip zero terms.
+
+    ``fused``: a conv whose input has a Θ, or that carries a nonlinearity or an addend, is one
+    cgp_covntk_conv_* launch when both streams' blocks fit its LDS cap at ``itemsize`` bytes
+    per element; otherwise, and with fused=False, it is the launch-by-launch sequence
+    (cgp_cov_conv_* on K, cgp_cov_conv_* on Θ with bias 0 and addend K', then
+    cgp_covntk_nonlin_* or the addends), which gives the same bits.  A conv downstream of an
+    AvgPool2d / CorrelatedConv2d keeps its nonlinearity as a launch of its own, as in
+    pool_steps.  A corrconv on Θ is cgp_corrconv_* with bias 0, then cgp_axpby_* adding K'."""
+    fwd = pool_steps(prog, v0, vf, body)
+    K = lambda v: ("K", v)                                                      # noqa: E731
+    steps = []
+    shapes = {}
+    scalar_vals = set(fwd.scalars)
+    scalars = set()
+    theta = {v0: None}
+
+    def emit(st, shape, scalar):
+        for b in st.writes():
+            shapes[b] = tuple(shape)
+            if scalar:
+                scalars.add(b)
+        steps.append(st)
+
+    for st in fwd.steps:
+        d, op = st.dst, st.op
+        shape, sc = fwd.shapes[d], d in scalar_vals
+        ts = theta.get(st.src) if st.src is not None else None
+        ta = theta.get(st.addend) if st.addend is not None else None
+        ka = K(st.addend) if st.addend is not None else None
+        if st.fn == "moments":
+            emit(PoolNtkStep("moments", K(d)), shape, sc)
+        elif st.fn == "conv":
+            g = op.geom
+            plain = st.post == N.CGP_COV_NONE and st.addend is None
+            if plain and ts is None:
+                emit(PoolNtkStep("conv", K(d), src=K(st.src), op=op, bias=g.bias), shape, sc)
+                theta[d] = K(d)
+            elif fused and conv_ntk_fits(g.taps, fwd.shapes[st.src][1],
+                                         1 if ts is None else 2, itemsize):
+                emit(PoolNtkStep("conv_ntk", K(d), src=K(st.src), op=op, post=st.post,
+                                 var=st.var, addend=ka, bias=g.bias, theta=ts,
+                                 dst_theta=("T", d), addend_theta=ta), shape, sc)
+                theta[d] = ("T", d)
+            else:
+                pre = d if plain else (st.var if st.post != N.CGP_COV_NONE else ("pre", d))
+                emit(PoolNtkStep("conv", K(pre), src=K(st.src), op=op, bias=g.bias), shape, sc)
+                tpre = K(pre)
+                if ts is not None:
+                    tpre = ("T", pre)
+                    emit(PoolNtkStep("conv", tpre, src=ts, op=op, bias=0.0, addend=K(pre)),
+                         shape, sc)
+                if plain:
+                    theta[d] = tpre
+                elif st.post != N.CGP_COV_NONE:
+                    emit(PoolNtkStep("nonlin_ntk", K(d), src=K(pre), op=op, post=st.post,
+                                     var=st.var, addend=ka, theta=tpre, dst_theta=("T", d),
+                                     addend_theta=ta), shape, sc)
+                    theta[d] = ("T", d)
+                else:
+                    emit(PoolNtkStep("axpby", K(d), op=op, terms=[(None, K(pre)), (None, ka)]),
+                         shape, sc)
+                    if ta is None:
+                        theta[d] = tpre
+                    else:
+                        emit(PoolNtkStep("axpby", ("T", d), op=op,
+                                         terms=[(None, tpre), (None, ta)]), shape, sc)
+                        theta[d] = ("T", d)
+        elif st.fn in ("nonlin", "gelu"):
+            if ts is None:
+                emit(PoolNtkStep(st.fn, K(d), src=K(st.src), op=op, post=st.post, var=st.var,
+                                 addend=ka), shape, sc)
+                theta[d] = ta
+            else:
+                emit(PoolNtkStep("nonlin_ntk", K(d), src=K(st.src), op=op,
+                                 post=N.CGP_COV_GELU if st.fn == "gelu" else st.post,
+                                 var=st.var, addend=ka, theta=ts, dst_theta=("T", d),
+                                 addend_theta=ta), shape, sc)
+                theta[d] = ("T", d)
+        elif st.fn in ("pool", "avgpool"):
+            emit(PoolNtkStep(st.fn, K(d), src=K(st.src), op=op), shape, sc)
+            theta[d] = None
+            if ts is not None:
+                emit(PoolNtkStep(st.fn, ("T", d), src=ts, op=op), shape, sc)
+                theta[d] = ("T", d)
+        elif st.fn == "corrconv":
+            emit(PoolNtkStep("corrconv", K(d), src=K(st.src), op=op, bias=op.geom.bias),
+                 shape, sc)
+            theta[d] = K(d)
+            if ts is not None:
+                emit(PoolNtkStep("corrconv", ("T", d), src=ts, op=op, bias=0.0), shape, sc)
+                emit(PoolNtkStep("accum", ("T", d), src=K(d), op=op), shape, sc)
+                theta[d] = ("T", d)
+        elif st.fn == "axpby":
+            emit(PoolNtkStep("axpby", K(d), op=op, terms=[(c, K(t)) for c, t in st.terms]),
+                 shape, sc)
+            live = [(c, theta[t]) for c, t in st.terms if theta[t] is not None]
+            if not live:
+                theta[d] = None
+            elif len(live) == 1 and live[0][0] is None:
+                theta[d] = live[0][1]
+            else:
+                emit(PoolNtkStep("axpby", ("T", d), op=op, terms=live), shape, sc)
+                theta[d] = ("T", d)
+        else:
+            raise AssertionError(st.fn)
+
+    last = {}
+    for idx, st in enumerate(steps):
+        for b in st.reads():
+            last[b] = idx
+    final, final_theta = K(vf), theta[vf]
+    last[final] = len(steps)
+    if final_theta is not None:
+        last[final_theta] = len(steps)
+    ns = PoolNtkSteps(steps, shapes, frozenset(b for b in shapes if b not in scalars),
+                      frozenset(scalars), final, final_theta, fwd.need_var, 0, fwd, fused)
+    live = set()
+    for idx, st in enumerate(steps):
+        live.update(st.writes())
+        ns.peak = max(ns.peak, sum(ns.elems(b) for b in live))
+        st.free = sorted((b for b in live if last.get(b, -1) <= idx), key=repr)
+        live.difference_update(st.free)
+    return ns
+
+
+# ------------------------------------------------------------------------------------
 # execution
 # ------------------------------------------------------------------------------------
 def _adjacent(x, y) -> bool:
@@ -1138,6 +1355,156 @@ class Plan:
             torch.cuda.synchronize(dev)
             cache[key] = tabs
         return tabs
+
+    def pool_ntk(self, body: bool, fused: bool, itemsize: int) -> PoolNtkSteps:
+        """pool_ntk_steps of the plan's program, cached per (body, fused, itemsize)."""
+        cache = self.__dict__.setdefault("_pool_ntk", {})
+        key = (bool(body), bool(fused), int(itemsize))
+        if key not in cache:
+            cache[key] = pool_ntk_steps(self.prog, self.v0, self.vf, body=body, fused=fused,
+                                        itemsize=itemsize)
+        return cache[key]
+
+    def run_pairs_pool_ntk(self, x, y, var, pair_i, pair_j, same, stream, ns, max_bytes=None):
+        """Runs ``ns`` (pool_ntk_steps) over the pairs (pair_i[m], pair_j[m]) -- device int32
+        arrays -- in chunks of pairs, like run_pairs_pool; returns (K, Θ) of the final value
+        of every pair as [npairs, elements] tensors, Θ None when it is zero (a model without
+        a conv).  var: the variance maps of ns.need_var (run_variances, and run_self_variances
+        on ns.forward for the values downstream of an AvgPool2d).  A chunk takes ns.peak
+        elements per pair, both streams counted; the result does not depend on the
+        chunking."""
+        sfx = self._sfx(x.dtype)
+        lib = N.load()
+        dev = x.device
+        item = x.element_size()
+        npairs = pair_i.numel()
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        per_pair = ns.peak * item
+        chunk = int(max_bytes) // per_pair
+        if chunk < 1:
+            big = max(ns.elems(b) for b in ns.shapes)
+            raise RuntimeError(
+                f"ntk_maps: one image pair needs {per_pair} bytes of position-pair maps "
+                f"({ns.peak} live elements of {item} bytes at the fullest launch, K and Θ; the "
+                f"largest map holds {big}), more than the workspace of {int(max_bytes)} bytes "
+                "(set_pool_workspace)")
+        chunk = min(chunk, npairs, max(1, (1 << 40) // max(ns.elems(b) for b in ns.shapes)))
+        C = x.shape[1]
+        out_k = torch.empty((npairs, ns.elems(ns.final)), dtype=x.dtype, device=dev)
+        out_t = None
+        if ns.final_theta is not None and ns.final_theta != ns.final:
+            out_t = torch.empty_like(out_k)
+        axpby = f"cgp_axpby_{sfx}"
+        for a in range(0, npairs, chunk):
+            n = min(chunk, npairs - a)
+            pi, pj = pair_i[a:a + n], pair_j[a:a + n]
+            bufs = {}
+
+            def new(b):
+                if b in bufs:                          # fn "accum" writes in place
+                    return bufs[b]
+                if b == ns.final:
+                    bufs[b] = out_k[a:a + n]
+                elif out_t is not None and b == ns.final_theta:
+                    bufs[b] = out_t[a:a + n]
+                else:
+                    bufs[b] = torch.empty((n, ns.elems(b)), dtype=x.dtype, device=dev)
+                return bufs[b]
+
+            def get(b):
+                return None if b is None else N.ptr(bufs[b])
+
+            for st in ns.steps:
+                h, w = ns.shapes[st.dst]
+                ne = ns.elems(st.dst)
+                dst = new(st.dst)
+                if st.fn == "moments":
+                    N.check(getattr(lib, f"cgp_cov_moments_{sfx}")(
+                        N.ptr(x), N.ptr(y), N.ptr(pi), N.ptr(pj), n, C, h, w, N.ptr(dst),
+                        stream), "cgp_cov_moments")
+                elif st.fn in ("conv", "conv_ntk"):
+                    g = st.op.geom
+                    ntk = st.fn == "conv_ntk"
+                    r = N.CovConvNtkArgs() if ntk else N.CovConvArgs()
+                    r.in_, r.out, r.addend = get(st.src), N.ptr(dst), get(st.addend)
+                    if ntk:
+                        r.theta, r.out_theta = get(st.theta), N.ptr(new(st.dst_theta))
+                        r.addend_theta = get(st.addend_theta)
+                    if st.var is not None:
+                        vx, vy = var[st.var]
+                        r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
+                    (r.h, r.w), r.ho, r.wo = ns.shapes[st.src], h, w
+                    r.taps, r.offset, r.stride, r.dilation = g.taps, g.offset, g.stride, \
+                        g.dilation
+                    r.post, r.same, r.flags = st.post, int(same), self.flags
+                    r.weight, r.bias = g.weight, st.bias
+                    what = "cgp_covntk_conv" if ntk else "cgp_cov_conv"
+                    N.check(getattr(lib, f"{what}_{sfx}")(r, stream), what)
+                elif st.fn == "nonlin_ntk":
+                    vx, vy = var[st.var]
+                    r = N.CovNonlinNtkArgs()
+                    r.in_, r.theta, r.out = get(st.src), get(st.theta), N.ptr(dst)
+                    r.out_theta = N.ptr(new(st.dst_theta))
+                    r.addend, r.addend_theta = get(st.addend), get(st.addend_theta)
+                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
+                    r.h, r.w, r.kind, r.same, r.flags = h, w, st.post, int(same), self.flags
+                    N.check(getattr(lib, f"cgp_covntk_nonlin_{sfx}")(r, stream),
+                            "cgp_covntk_nonlin")
+                elif st.fn == "nonlin":
+                    vx, vy = var[st.var]
+                    r = N.CovNonlinArgs()
+                    r.in_, r.out, r.addend = get(st.src), N.ptr(dst), get(st.addend)
+                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
+                    r.h, r.w, r.kind, r.same, r.flags = h, w, st.post, int(same), self.flags
+                    N.check(getattr(lib, f"cgp_cov_nonlin_{sfx}")(r, stream), "cgp_cov_nonlin")
+                elif st.fn == "gelu":
+                    vx, vy = var[st.var]
+                    r = N.GeluCovArgs()
+                    r.in_, r.out, r.addend = get(st.src), N.ptr(dst), get(st.addend)
+                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
+                    r.h, r.w, r.same = h, w, int(same)
+                    N.check(getattr(lib, f"cgp_gelu_cov_{sfx}")(r, stream), "cgp_gelu_cov")
+                elif st.fn == "pool":
+                    N.check(getattr(lib, f"cgp_cov_pool_{sfx}")(
+                        get(st.src), n, ns.elems(st.src), N.ptr(dst), stream), "cgp_cov_pool")
+                elif st.fn == "avgpool":
+                    r = N.CovAvgPoolArgs()
+                    r.in_, r.out, r.npairs = get(st.src), N.ptr(dst), n
+                    (r.h, r.w), r.ho, r.wo = ns.shapes[st.src], h, w
+                    r.k, r.stride = st.op.geom.taps, st.op.geom.stride
+                    N.check(getattr(lib, f"cgp_covmap_avgpool_{sfx}")(r, stream),
+                            "cgp_covmap_avgpool")
+                elif st.fn == "corrconv":
+                    g = st.op.geom
+                    rr, rc = self._corr_tables(st.op, dev, x.dtype)
+                    r = N.CorrConvArgs()
+                    r.in_, r.out, r.npairs = get(st.src), N.ptr(dst), n
+                    r.corr_rows, r.corr_cols = N.ptr(rr), N.ptr(rc)
+                    (r.h, r.w), r.ho, r.wo = ns.shapes[st.src], h, w
+                    r.taps, r.offset, r.stride, r.dilation = g.taps, g.offset, g.stride, g.dilation
+                    r.weight, r.bias = g.weight, st.bias
+                    N.check(getattr(lib, f"cgp_corrconv_{sfx}")(r, stream), "cgp_corrconv")
+                elif st.fn == "accum":
+                    N.call(axpby, 1.0, N.ptr(dst), 1.0, get(st.src), N.ptr(dst), n * ne, stream)
+                elif st.fn == "axpby":
+                    for k, (coef, b) in enumerate(st.terms):
+                        c = 1.0 if coef is None else coef
+                        if k == 0:
+                            N.call(axpby, c, get(b), 0.0, None, N.ptr(dst), n * ne, stream)
+                        else:
+                            N.call(axpby, 1.0, N.ptr(dst), c, get(b), N.ptr(dst), n * ne, stream)
+                else:
+                    raise AssertionError(st.fn)
+                for b in st.free:
+                    del bufs[b]
+        if ns.final_theta == ns.final:
+            out_t = out_k.clone()
+        return out_k, out_t
 
     def run_self_variances(self, x, var, stream, ps=None, max_bytes=None, want=None):
         """The variance maps [n, h, w] of the values ``want`` (default ps.self_var: what the

@@ -628,6 +628,17 @@ __device__ __forceinline__ T relu_pair(T c, const T* __restrict__ xx, const T* _
     return exact ? relu_exact(c, v1, v2) : relu_fast(c, v1, v2);
 }
 
+// The ReLU's NTK factor κ̇ = dK'/dc at fixed variances (cgp_relu_ntk_*, cgp_covntk_nonlin_*).
+// exact: the reference's op sequence for theta (correctly rounded 1/sqrt, relu_exact's);
+// else the Newton-refined hardware rsq of the closed-form ReLU.  Every op rounded in T.
+template <typename T>
+__device__ __forceinline__ T relu_kdot(T c, T v1, T v2, int exact) {
+    const T t = v1 * v2 + K<T>::tiny;                       // :146
+    T cs = exact ? c * (T(1) / sqrt_t(t)) : c * rsqrt_fast(t);   // :149
+    cs = cs < T(-1) ? T(-1) : (cs > T(1) ? T(1) : cs);      // clamp(-1, 1), NaN kept
+    return (K<T>::pi - acos_t(cs)) / K<T>::two_pi;          // :151
+}
+
 // ----------------------------------------------------------------------------------
 // erf networks (include/cnngp.h): one function per stream, shared by every
 // caller.  One evaluation mode: correctly rounded division and square root, the device
@@ -680,6 +691,30 @@ __device__ __forceinline__ void pair_of(unsigned m, const FastDiv& n2, int diag,
         i = fdiv(m, n2);
         j = m - i * n2.d;
     }
+}
+
+// position-pair maps [pair][p_row][q_row][p_col][q_col] (include/cnngp.h): element of one
+// pair's map -> pixels p = p_row·w + p_col, q = q_row·w + q_col
+struct CovIdx {
+    FastDiv dn, dww, dh, dw;   // (h·w)², w², h, w
+    int w;
+};
+inline CovIdx make_idx(int h, int w) {
+    CovIdx g;
+    g.dn = make_fastdiv((unsigned)((long long)h * w * h * w));
+    g.dww = make_fastdiv((unsigned)(w * w));
+    g.dh = make_fastdiv((unsigned)h);
+    g.dw = make_fastdiv((unsigned)w);
+    g.w = w;
+    return g;
+}
+__device__ __forceinline__ void cov_decode(const CovIdx& g, unsigned r, int& p, int& q) {
+    const unsigned rp = fdiv(r, g.dww);            // p_row·h + q_row
+    const unsigned in = r - rp * g.dww.d;          // p_col·w + q_col
+    const unsigned pr = fdiv(rp, g.dh), qr = rp - pr * g.dh.d;
+    const unsigned pc = fdiv(in, g.dw), qc = in - pc * g.dw.d;
+    p = (int)(pr * g.w + pc);
+    q = (int)(qr * g.w + qc);
 }
 
 // LDS-only barrier: waits for this wave's LDS traffic, not for its global loads, so the

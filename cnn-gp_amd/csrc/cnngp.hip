@@ -652,16 +652,6 @@ struct ReluNtkP {
     int hw, same, diag, exact, mpb;
 };
 
-// exact: the reference's op sequence for theta (correctly rounded 1/sqrt, relu_exact's);
-// else the Newton-refined hardware rsq of the closed-form ReLU.  Every op rounded in T.
-template <typename T>
-__device__ __forceinline__ T relu_kdot(T c, T v1, T v2, int exact) {
-    const T t = v1 * v2 + K<T>::tiny;                       // :146
-    T cs = exact ? c * (T(1) / sqrt_t(t)) : c * rsqrt_fast(t);   // :149
-    cs = cs < T(-1) ? T(-1) : (cs > T(1) ? T(1) : cs);      // clamp(-1, 1), NaN kept
-    return (K<T>::pi - acos_t(cs)) / K<T>::two_pi;          // :151
-}
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void relu_ntk_kernel(const ReluNtkP<T> p) {
     const long long m0 = (long long)blockIdx.x * p.mpb;

@@ -33,29 +33,6 @@ constexpr int kPoolBlock = 1024;              // threads of a pool workgroup (on
 constexpr int kMaxLds = 64 * 1024;            // bytes of LDS one conv workgroup may take
 constexpr long long kMaxPairElems = 1LL << 30;   // (h·w)² of one pair: 32-bit index math
 
-// element of one pair's map -> pixels p = p_row·w + p_col, q = q_row·w + q_col
-struct CovIdx {
-    FastDiv dn, dww, dh, dw;   // (h·w)², w², h, w
-    int w;
-};
-CovIdx make_idx(int h, int w) {
-    CovIdx g;
-    g.dn = make_fastdiv((unsigned)((long long)h * w * h * w));
-    g.dww = make_fastdiv((unsigned)(w * w));
-    g.dh = make_fastdiv((unsigned)h);
-    g.dw = make_fastdiv((unsigned)w);
-    g.w = w;
-    return g;
-}
-__device__ __forceinline__ void cov_decode(const CovIdx& g, unsigned r, int& p, int& q) {
-    const unsigned rp = fdiv(r, g.dww);            // p_row·h + q_row
-    const unsigned in = r - rp * g.dww.d;          // p_col·w + q_col
-    const unsigned pr = fdiv(rp, g.dh), qr = rp - pr * g.dh.d;
-    const unsigned pc = fdiv(in, g.dw), qc = in - pc * g.dw.d;
-    p = (int)(pr * g.w + pc);
-    q = (int)(qr * g.w + qc);
-}
-
 // The nonlinearity's map of (c, v1, v2) = (S[p, q], xx_i[p], yy_j[q]) with the device
 // functions of the layer kernels.  The reference's override (kernels.py:155-162) applies
 // where the two arguments are the same pre-activation: same, i == j and p == q.

@@ -104,30 +104,8 @@ __global__ __launch_bounds__(kBlock) void var_gelu_kernel(const T* __restrict__ 
 // ----------------------------------------------------------------------------------
 // position-pair maps [pair][p_row][q_row][p_col][q_col]: element -> pixels
 // p = p_row·w + p_col, q = q_row·w + q_col; one kChunk-element chunk per workgroup, which
-// may straddle pairs
+// may straddle pairs (CovIdx, cov_decode: cgp_common.h)
 // ----------------------------------------------------------------------------------
-struct CovIdx {
-    FastDiv dn, dww, dh, dw;   // (h·w)², w², h, w
-    int w;
-};
-CovIdx make_idx(int h, int w) {
-    CovIdx g;
-    g.dn = make_fastdiv((unsigned)((long long)h * w * h * w));
-    g.dww = make_fastdiv((unsigned)(w * w));
-    g.dh = make_fastdiv((unsigned)h);
-    g.dw = make_fastdiv((unsigned)w);
-    g.w = w;
-    return g;
-}
-__device__ __forceinline__ void cov_decode(const CovIdx& g, unsigned r, int& p, int& q) {
-    const unsigned rp = fdiv(r, g.dww);            // p_row·h + q_row
-    const unsigned in = r - rp * g.dww.d;          // p_col·w + q_col
-    const unsigned pr = fdiv(rp, g.dh), qr = rp - pr * g.dh.d;
-    const unsigned pc = fdiv(in, g.dw), qc = in - pc * g.dw.d;
-    p = (int)(pr * g.w + pc);
-    q = (int)(qr * g.w + qc);
-}
-
 template <typename T>
 struct GeluCovP {
     const T* in;

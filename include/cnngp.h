@@ -493,6 +493,90 @@ int cgp_gelu_cov_f64(const cgp_gelu_cov_args* args, void* stream);
 int cgp_gelu_cov_f32(const cgp_gelu_cov_args* args, void* stream);
 
 /*
+ * The NTK on position-pair maps (additions to ABI 12: no struct or existing entry point
+ * changed).  A second map Θ[m][p, q] travels beside S[m][p, q], in the layout and
+ * with the conventions of "Position-pair maps" above.  Every linear entry point there
+ * (cgp_cov_conv_* with an addend, cgp_covmap_avgpool_*, cgp_corrconv_*, cgp_cov_pool_*,
+ * cgp_axpby_*) is linear in its input and serves Θ as it is; the two below are the steps that
+ * need both streams.  CGP_COV_GELU is valid in these two entry points only (the forward GELU
+ * is cgp_gelu_cov_*).
+ */
+#define CGP_COV_GELU 3   /* the map of cgp_gelu_* */
+/*
+ * The nonlinearity step on both streams in one pass:
+ *   out       = map(in) [+ addend]          the bits of cgp_cov_nonlin_* / cgp_gelu_cov_*
+ *   out_theta = theta·κ̇ [+ addend_theta]    each a separate rounding
+ * with (c, v1, v2) = (in[m][p, q], xx[pair_i[m]][p], yy[pair_j[m]][q]) and κ̇ = d map / dc at
+ * fixed variances, the layer path's: cgp_relu_ntk_*'s (π - θ)/2π (honours
+ * CGP_FLAG_EXACT_RELU), cgp_erf_*'s (4/π)/√D, cgp_gelu_*'s.  Where same, pair_i[m] ==
+ * pair_j[m] and p == q, out is the variance map's value and κ̇ the layer path's override:
+ * exactly 1/2 (ReLU), (4/π)/√(1 + 4v) (erf), the GELU line at c = v1 = v2 = v.
+ * theta may be in (the first nonlinearity after the first conv, where Θ is K's buffer), and
+ * in-place (out == in, out_theta == theta) is allowed: every element is read before it is
+ * written, by one thread.  out and out_theta are two buffers.
+ */
+typedef struct cgp_covntk_nonlin_args {
+    const void* in;            /* [npairs][h][h][w][w] */
+    const void* theta;         /* like in */
+    void* out;
+    void* out_theta;
+    const void* addend;        /* like out, or NULL */
+    const void* addend_theta;  /* like out_theta, or NULL */
+    const void* xx;            /* [n1][h][w] variances at the nonlinearity's input */
+    const void* yy;            /* [n2][h][w] (same: may be xx) */
+    const int32_t* pair_i;     /* device [npairs] */
+    const int32_t* pair_j;
+    int64_t npairs;
+    int32_t h, w;
+    int32_t kind;              /* CGP_COV_RELU, CGP_COV_ERF or CGP_COV_GELU */
+    int32_t same;
+    int32_t flags;             /* CGP_FLAG_EXACT_RELU (ReLU only) */
+    int32_t reserved;
+} cgp_covntk_nonlin_args;
+size_t cgp_covntk_nonlin_args_size(void);
+int cgp_covntk_nonlin_f64(const cgp_covntk_nonlin_args* args, void* stream);
+int cgp_covntk_nonlin_f32(const cgp_covntk_nonlin_args* args, void* stream);
+/*
+ * Conv2d on both streams from one staging: with A the stencil sum of cgp_cov_conv_* (column
+ * taps first, then row taps, left to right),
+ *   k' = weight·A(in) + bias
+ *   t' = weight·A(theta) + k'            the product rounded, then the sum
+ * and then, with post in {CGP_COV_RELU, CGP_COV_ERF, CGP_COV_GELU}, the nonlinearity step
+ * above on (k', t') with xx / yy = the variances of the conv output:
+ *   out = map(k') [+ addend],  out_theta = t'·κ̇(k') [+ addend_theta]
+ * or, with post == CGP_COV_NONE, out = k' [+ addend], out_theta = t' [+ addend_theta].
+ * out has the bits of cgp_cov_conv_*; out_theta has the bits of the launch-by-launch sequence
+ * (cgp_cov_conv_* on theta with bias 0 and addend k', then cgp_covntk_nonlin_*).
+ * theta == NULL is Θ = 0 upstream (the first conv): t' = k', and nothing is staged for Θ.
+ * out / out_theta must not be in / theta, nor each other.  One workgroup stages `taps` w×w
+ * blocks of each stream it reads: streams·taps·w²·itemsize must not exceed 64 KB, checked
+ * before any launch.  A 1×1 value (h = w = 1) is a map like any other.
+ */
+typedef struct cgp_covntk_conv_args {
+    const void* in;            /* [npairs][h][h][w][w] */
+    const void* theta;         /* like in, or NULL: Θ = 0 */
+    void* out;                 /* [npairs][ho][ho][wo][wo] */
+    void* out_theta;           /* like out */
+    const void* addend;        /* like out, or NULL */
+    const void* addend_theta;  /* like out_theta, or NULL */
+    const void* xx;            /* post != CGP_COV_NONE: [n1][ho][wo], else unused */
+    const void* yy;            /* post != CGP_COV_NONE: [n2][ho][wo] (same: may be xx) */
+    const int32_t* pair_i;     /* device [npairs]; read only with a post-nonlinearity */
+    const int32_t* pair_j;
+    int64_t npairs;
+    int32_t h, w, ho, wo;
+    int32_t taps, offset, stride, dilation;   /* as cgp_conv_args */
+    int32_t post;              /* CGP_COV_* */
+    int32_t same;
+    int32_t flags;             /* CGP_FLAG_EXACT_RELU */
+    int32_t reserved;
+    double weight, bias;
+} cgp_covntk_conv_args;
+size_t cgp_covntk_conv_args_size(void);
+int cgp_covntk_conv_f64(const cgp_covntk_conv_args* args, void* stream);
+int cgp_covntk_conv_f32(const cgp_covntk_conv_args* args, void* stream);
+
+/*
  * out = alpha·a + beta·b (b may be NULL: out = alpha·a), n elements.  The unfused form
  * of Sum (alpha = beta = 1, kernel_patch.py:43-63) and Mixture (kernels.py:220-225).
  * Products and the sum are rounded separately (no FMA contraction), like torch.
