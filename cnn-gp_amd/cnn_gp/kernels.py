@@ -40,6 +40,39 @@ def _to_device(t: torch.Tensor, device) -> torch.Tensor:
     return t.contiguous()
 
 
+def _check_1x1(plan):
+    """kernels.py:53-57: the kernel of a pair is the final value's one pixel."""
+    if plan.final_hw != (1, 1):
+        raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
+                           " per pair, not 1x1: add a final Conv2d covering the map")
+
+
+def _pair_results(r, pi, pj, n1, n2, same, diag):
+    """The [npairs] results of a run on position-pair maps as [n1] (diag), [n1, n2], or, from
+    the pairs i <= j of a same tile, [n1, n1] mirrored: symmetric bit for bit."""
+    if diag:
+        return r.view(n1)
+    if not same:
+        return r.view(n1, n2)
+    k = torch.empty((n1, n1), dtype=r.dtype, device=r.device)
+    k[pj, pi] = r.view(-1)
+    k[pi, pj] = r.view(-1)
+    return k
+
+
+def _pair_maps(r, pi, pj, lead, ho, wo, same, diag):
+    """The [npairs, elements] maps of a run as ``lead`` + (p_row, p_col, q_row, q_col) from the
+    internal layout [p_row][q_row][p_col][q_col]; on a same tile the pairs i > j are the
+    mirror X_ji[q, p] = X_ij[p, q]."""
+    r = r.view(-1, ho, ho, wo, wo).permute(0, 1, 3, 2, 4)
+    if not same or diag:
+        return r.reshape(lead + (ho, wo, ho, wo))
+    s = torch.empty(lead + (ho, wo, ho, wo), dtype=r.dtype, device=r.device)
+    s[pj, pi] = r.permute(0, 3, 4, 1, 2)
+    s[pi, pj] = r
+    return s
+
+
 class _ImageVariances:
     """Variance maps of one image set for one Gram build (NNGPKernel.image_variances):
     var[v] = [N, h, w] maps of every value the whole-network kernel reads, and what the
@@ -311,9 +344,7 @@ class NNGPKernel(nn.Module):
         n1, c, h, w = x.shape
         n2 = y.shape[0]
         plan = self._plan(h, w)
-        if plan.final_hw != (1, 1):                              # kernels.py:53-57
-            raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
-                               " per pair, not 1x1: add a final Conv2d covering the map")
+        _check_1x1(plan)
         if not any(o.kind == "conv" for o in plan.prog.ops):
             # no Conv2d, no parameters: Θ = 0 and there is no second stream to carry, so K
             # is forward's own run, bit for bit whichever path forward takes (the
@@ -349,19 +380,9 @@ class NNGPKernel(nn.Module):
         sfx = Plan._sfx(x.dtype)
         lib = N.load()
         if plan.pool is not None:     # GlobalAvgPool, AvgPool2d, CorrelatedConv2d: DESIGN §3.3-5
-            if plan.final_hw != (1, 1):                          # kernels.py:53-57
-                raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
-                                   " per pair, not 1x1: add a final Conv2d covering the map")
-            r, pi, pj = self._run_pool(plan, plan.pool, x, y, same, diag, stream)
-            if diag:
-                return r.view(n1)
-            if not same:
-                return r.view(n1, n2)
-            # the pairs i <= j, mirrored: K is symmetric bit for bit
-            k = torch.empty((n1, n1), dtype=x.dtype, device=x.device)
-            k[pj, pi] = r.view(-1)
-            k[pi, pj] = r.view(-1)
-            return k
+            _check_1x1(plan)
+            r, _, pi, pj = self._run_cov(plan, plan.pool, x, y, same, diag, stream)
+            return _pair_results(r, pi, pj, n1, n2, same, diag)
         if diag and same and VAR_CHAIN and self._net_plan(plan, x.element_size()) is not None:
             # same and diag: the reference overrides every K' with the image's own variance
             # (kernels.py:134-165), so the result IS the variance chain's final value — the
@@ -405,21 +426,33 @@ class NNGPKernel(nn.Module):
                                                            int(diag), N.ptr(xy0), stream),
                     "cgp_moments_xy")
         out = plan.run_pairs(x, y, xy0, var, n1, n2, same, diag, stream)
-        if plan.final_hw != (1, 1):                              # kernels.py:53-57
-            raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
-                               " per pair, not 1x1: add a final Conv2d covering the map")
+        _check_1x1(plan)
         return out.view(n1) if diag else out.view(n1, n2)
 
-    # ---- GlobalAvgPool: position-pair maps ------------------------------------------
-    def _run_pool(self, plan, ps, x, y, same, diag, stream):
-        """Runs the launch list ``ps`` (program.pool_steps) on the pairs of a tile: all of
-        them, the pairs i <= j of a same tile, or (i, i) for diag.  Returns (the final value
-        of every pair [npairs, elements], pair_i, pair_j) with the pair lists as int64
-        index tensors."""
-        pi, pj, var, ws = self._pool_pairs(plan, ps, x, y, same, diag, stream)
-        r = plan.run_pairs_pool(x, y, var, pi.to(torch.int32), pj.to(torch.int32), same, stream,
-                                ps, ws)
-        return r, pi, pj
+    # ---- position-pair maps: GlobalAvgPool, AvgPool2d, CorrelatedConv2d and their NTK ----
+    def _on_compute_device(self, x, y, run):
+        """run(x, y, stream) with the images on the compute device and that device current;
+        the tensors it returns, moved back to where x lives."""
+        out_device = x.device
+        dev = self._compute_device(x)
+        with torch.cuda.device(dev):
+            xd = _to_device(x, dev)
+            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
+            outs = run(xd, yd, _stream_handle(dev))
+        return [o.to(out_device) for o in outs] if out_device != dev else outs
+
+    def _run_cov(self, plan, cs, x, y, same, diag, stream):
+        """Runs the launch list ``cs`` (program.pool_steps or pool_ntk_steps) on the pairs of a
+        tile: all of them, the pairs i <= j of a same tile, or (i, i) for diag.  Returns
+        (K, Θ, pair_i, pair_j): the final value of every pair [npairs, elements] -- Θ None for
+        a forward list, zeros for a model without a conv -- and the pair lists as int64 index
+        tensors."""
+        pi, pj, var, ws = self._pool_pairs(plan, cs.forward or cs, x, y, same, diag, stream)
+        k, th = plan.run_cov_steps(cs, x, y, var, pi.to(torch.int32), pj.to(torch.int32), same,
+                                   stream, ws)
+        if th is None and cs.forward is not None:
+            th = torch.zeros_like(k)
+        return k, th, pi, pj
 
     def _pool_pairs(self, plan, ps, x, y, same, diag, stream):
         """The pair lists of a tile (int64 index tensors), the variance maps ``ps`` reads
@@ -430,7 +463,7 @@ class NNGPKernel(nn.Module):
         if diag:
             pi = pj = torch.arange(n1, device=dev)
         elif same:
-            pi, pj = torch.triu_indices(n1, n1, device=dev)
+            pi, pj = torch.triu_indices(n1, n1, device=dev)     # _pair_results mirrors them
         else:
             pi = torch.arange(n1, device=dev).repeat_interleave(n2)
             pj = torch.arange(n2, device=dev).repeat(n1)
@@ -454,7 +487,6 @@ class NNGPKernel(nn.Module):
             var.update({v: (sx[v], sy[v]) for v in ps.self_var})
         return pi, pj, var, ws
 
-    # ---- the NTK on position-pair maps ---------------------------------
     def set_ntk_maps_fusion(self, enabled: bool):
         """Lower the convs of ntk_maps / position_ntk to the two-stream cgp_covntk_conv_*
         (default) or to the launch-by-launch sequence; the results are the same bits."""
@@ -462,15 +494,10 @@ class NNGPKernel(nn.Module):
             m.__dict__["_cgp_ntk_maps_fused"] = bool(enabled)
         return self
 
-    def _run_pool_ntk(self, plan, body, x, y, same, diag, stream):
-        """(K, Θ, pair_i, pair_j) of the tile's pairs through program.pool_ntk_steps; K and Θ
-        [npairs, elements], Θ zeros for a model without a conv."""
-        ns = plan.pool_ntk(body, getattr(self, "_cgp_ntk_maps_fused", NTK_MAPS_FUSED),
-                           x.element_size())
-        pi, pj, var, ws = self._pool_pairs(plan, ns.forward, x, y, same, diag, stream)
-        k, th = plan.run_pairs_pool_ntk(x, y, var, pi.to(torch.int32), pj.to(torch.int32), same,
-                                        stream, ns, ws)
-        return k, (torch.zeros_like(k) if th is None else th), pi, pj
+    def _ntk_maps_steps(self, plan, body, x):
+        """program.pool_ntk_steps of the plan as set_ntk_maps_fusion and x's dtype have it."""
+        return plan.pool_ntk(body, getattr(self, "_cgp_ntk_maps_fused", NTK_MAPS_FUSED),
+                             x.element_size())
 
     def ntk_maps(self, x, y=None, same=None, diag=False, return_nngp=False):
         """The neural tangent kernel Θ, [N1, N2] (or [N1] when diag), carried on position-pair
@@ -499,32 +526,17 @@ class NNGPKernel(nn.Module):
         plan.pool_ntk(body, True, 8)                  # the lowering's rejections come first
         if empty is not None:
             return (empty, empty.clone()) if return_nngp else empty
-        out_device = x.device
-        dev = self._compute_device(x)
-        if plan.final_hw != (1, 1):                              # kernels.py:53-57
-            raise RuntimeError(f"the model's output is {plan.final_hw[0]}x{plan.final_hw[1]}"
-                               " per pair, not 1x1: add a final Conv2d covering the map")
-        n1, n2 = len(x), len(y)
-        with torch.no_grad(), torch.cuda.device(dev):
-            xd = _to_device(x, dev)
-            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
-            k, th, pi, pj = self._run_pool_ntk(plan, body, xd, yd, same, diag,
-                                               _stream_handle(dev))
-            outs = []
-            for r in (k, th):
-                if diag:
-                    outs.append(r.view(n1))
-                elif not same:
-                    outs.append(r.view(n1, n2))
-                else:
-                    # the pairs i <= j, mirrored: symmetric bit for bit
-                    full = torch.empty((n1, n1), dtype=x.dtype, device=dev)
-                    full[pj, pi] = r.view(-1)
-                    full[pi, pj] = r.view(-1)
-                    outs.append(full)
-        if out_device != dev:
-            outs = [o.to(out_device) for o in outs]
-        return (outs[0], outs[1]) if return_nngp else outs[1]
+        self._compute_device(x)                       # forward's order: no device, then
+        _check_1x1(plan)                              # a final value that is not 1x1
+
+        def run(xd, yd, stream):
+            k, th, pi, pj = self._run_cov(plan, self._ntk_maps_steps(plan, body, xd), xd, yd,
+                                          same, diag, stream)
+            return [_pair_results(r, pi, pj, len(x), len(y), same, diag) for r in (k, th)]
+
+        with torch.no_grad():
+            k, th = self._on_compute_device(x, y, run)
+        return (k, th) if return_nngp else th
 
     def position_ntk(self, x, y=None, same=None, diag=False, return_nngp=False):
         """position_covariance's twin for Θ: Θ[i, j, p, q] of a model without a GlobalAvgPool,
@@ -539,27 +551,15 @@ class NNGPKernel(nn.Module):
         if empty is not None:
             e = torch.empty(lead + (ho, wo, ho, wo), dtype=x.dtype, device=x.device)
             return (e, e.clone()) if return_nngp else e
-        out_device = x.device
-        dev = self._compute_device(x)
-        with torch.no_grad(), torch.cuda.device(dev):
-            xd = _to_device(x, dev)
-            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
-            k, th, pi, pj = self._run_pool_ntk(plan, True, xd, yd, same, diag,
-                                               _stream_handle(dev))
-            outs = []
-            for r in (k, th):
-                # internal layout [p_row][q_row][p_col][q_col] -> (p_row, p_col, q_row, q_col)
-                r = r.view(-1, ho, ho, wo, wo).permute(0, 1, 3, 2, 4)
-                if same and not diag:
-                    s = torch.empty(lead + (ho, wo, ho, wo), dtype=x.dtype, device=dev)
-                    s[pj, pi] = r.permute(0, 3, 4, 1, 2)         # Θ_ji[q, p] = Θ_ij[p, q]
-                    s[pi, pj] = r
-                else:
-                    s = r.reshape(lead + (ho, wo, ho, wo))
-                outs.append(s)
-        if out_device != dev:
-            outs = [o.to(out_device) for o in outs]
-        return (outs[0], outs[1]) if return_nngp else outs[1]
+
+        def run(xd, yd, stream):
+            s, th, pi, pj = self._run_cov(plan, self._ntk_maps_steps(plan, True, xd), xd, yd,
+                                          same, diag, stream)
+            return [_pair_maps(r, pi, pj, lead, ho, wo, same, diag) for r in (s, th)]
+
+        with torch.no_grad():
+            s, th = self._on_compute_device(x, y, run)
+        return (s, th) if return_nngp else th
 
     def position_covariance(self, x, y=None, same=None, diag=False):
         """The position-pair covariance map of the model's output: S[i, j, p, q], the
@@ -576,21 +576,12 @@ class NNGPKernel(nn.Module):
         lead = (len(x),) if diag else (len(x), len(y))
         if empty is not None:
             return torch.empty(lead + (ho, wo, ho, wo), dtype=x.dtype, device=x.device)
-        out_device = x.device
-        dev = self._compute_device(x)
-        with torch.cuda.device(dev):
-            xd = _to_device(x, dev)
-            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
-            r, pi, pj = self._run_pool(plan, ps, xd, yd, same, diag, _stream_handle(dev))
-            # internal layout [p_row][q_row][p_col][q_col] -> (p_row, p_col, q_row, q_col)
-            r = r.view(-1, ho, ho, wo, wo).permute(0, 1, 3, 2, 4)
-            if same and not diag:
-                s = torch.empty(lead + (ho, wo, ho, wo), dtype=x.dtype, device=dev)
-                s[pj, pi] = r.permute(0, 3, 4, 1, 2)             # S_ji[q, p] = S_ij[p, q]
-                s[pi, pj] = r
-            else:
-                s = r.reshape(lead + (ho, wo, ho, wo))
-        return s.to(out_device) if out_device != dev else s
+
+        def run(xd, yd, stream):
+            s, _, pi, pj = self._run_cov(plan, ps, xd, yd, same, diag, stream)
+            return [_pair_maps(s, pi, pj, lead, ho, wo, same, diag)]
+
+        return self._on_compute_device(x, y, run)[0]
 
     # ---- Gram builds: every image's variance maps once per build -------------------
     # The reference (and forward above) recomputes the per-image variance recursion

@@ -472,12 +472,16 @@ CORRCONV_RULE_NTK = ("ntk: the neural tangent kernel of a model with a Correlate
 
 
 @dataclasses.dataclass
-class PoolStep:
-    """One launch of a pooled run.  Buffers are named by the SSA value they hold.
+class CovStep:
+    """One launch of a run on position-pair maps.  pool_steps names a buffer by the SSA value
+    it holds; pool_ntk_steps by ("K", v) / ("T", v), the K and Θ maps of value v, as in
+    ntk_steps, with v = ("pre", d) for the conv output that a fused addend replaced in the
+    forward program.  Either list may hold
 
     fn "moments": dst = mean_c x[c, p]·y[c, q]                          cgp_cov_moments_*
     fn "conv":    dst = A(src)·weight + bias [→ ReLU, variances of value ``var``]
-                  [+ addend]                                             cgp_cov_conv_*
+                  [+ addend]; ``bias`` replaces the geometry's (0 on the Θ stream)
+                                                                         cgp_cov_conv_*
     fn "nonlin":  dst = relu / erf (``post``) of src, variances of value ``var``
                   [+ addend]                                             cgp_cov_nonlin_*
     fn "gelu":    dst = gelu of src, variances of value ``var`` [+ addend]
@@ -485,50 +489,101 @@ class PoolStep:
     fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
     fn "avgpool": dst = mean of src over the windows of p and of q (op.geom)
                                                                          cgp_covmap_avgpool_*
-    fn "corrconv": dst = the correlated-weight conv of src (op.geom)     cgp_corrconv_*
+    fn "corrconv": dst = the correlated-weight conv of src (op.geom, ``bias``)
+                                                                         cgp_corrconv_*
     fn "axpby":   dst = Σ coef·buffer over ``terms`` (coef None: 1)      cgp_axpby_*
+
+    and the two-stream list also
+    fn "conv_ntk":   dst, dst_theta = the two-stream conv of (src, theta), theta None for
+                     Θ = 0, [→ nonlinearity ``post``] [+ addend, + addend_theta]
+                                                                          cgp_covntk_conv_*
+    fn "nonlin_ntk": dst, dst_theta = ``post`` of src [+ addend], theta·κ̇ [+ addend_theta]
+                                                                          cgp_covntk_nonlin_*
+    fn "accum":      dst = dst + src, in place                            cgp_axpby_*
     ``free``: the buffers nothing reads after this launch."""
     fn: str
-    dst: int
-    src: Optional[int] = None
+    dst: object
+    src: Optional[object] = None
     op: Optional[Op] = None
     post: int = N.CGP_COV_NONE
     var: Optional[int] = None
-    addend: Optional[int] = None
+    addend: Optional[object] = None
+    bias: Optional[float] = None
+    theta: Optional[tuple] = None
+    dst_theta: Optional[tuple] = None
+    addend_theta: Optional[tuple] = None
     terms: list = dataclasses.field(default_factory=list)
     free: list = dataclasses.field(default_factory=list)
 
     def reads(self):
-        r = [b for b in (self.src, self.addend) if b is not None]
+        r = [b for b in (self.src, self.addend, self.theta, self.addend_theta)
+             if b is not None]
+        if self.fn == "accum":
+            r.append(self.dst)
         return r + [b for _, b in self.terms]
+
+    def writes(self):
+        return [b for b in (self.dst, self.dst_theta) if b is not None]
 
 
 @dataclasses.dataclass
-class PoolSteps:
+class CovSteps:
+    """A launch list on position-pair maps, pool_steps' or pool_ntk_steps' (there over the
+    buffers of both streams): what Plan.run_cov_steps runs."""
     steps: list
     shapes: dict        # buffer -> (h, w) of its value
     maps: frozenset     # buffers that are position-pair maps: (h·w)² elements per pair
     scalars: frozenset  # buffers downstream of the pool: one element per pair
-    pooled: frozenset   # every value of the unfused program at or after a pool
-    final: int
+    final: object
     need_var: frozenset  # values whose per-image variance maps the nonlinearities read
-    peak: int           # elements per pair live at the fullest launch
+    peak: int = 0       # elements per pair live at the fullest launch (_schedule)
+    largest: int = 0    # elements per pair of the largest buffer (_schedule)
+    # pool_steps only.  ``pooled``: every value of the unfused program at or after a pool.
     # AvgPool2d, CorrelatedConv2d (DESIGN §3.4, §3.5): the values of the unfused program at or
     # downstream of one (either ends the closure of the per-image variances), the
     # values of need_var among them -- their variance maps are the p = q diagonals of the
     # images' self maps, extracted by a pass of steps[:self_last + 1] over the pairs (i, i)
     # (run_self_variances) -- and the index of the step that writes the last of those
     # (-1: no self pass)
+    pooled: frozenset = frozenset()
     avgpooled: frozenset = frozenset()
     self_var: frozenset = frozenset()
     self_last: int = -1
+    # pool_ntk_steps only: the buffer that holds Θ of the final value (``final`` itself after
+    # a single conv, None for Θ = 0), the forward-only list of the same program (its self pass
+    # gives the variances downstream of an AvgPool2d) and the ``fused`` it was lowered with
+    final_theta: Optional[tuple] = None
+    forward: Optional["CovSteps"] = None
+    fused: bool = True
 
     def elems(self, b) -> int:
         h, w = self.shapes[b]
         return (h * w) ** 2 if b in self.maps else 1
 
 
-def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps:
+def _schedule(cs: CovSteps, keep, key=None):
+    """Sets every step's ``free`` -- the live buffers no later step reads, those of ``keep``
+    never, sorted by ``key`` -- and cs.peak and cs.largest."""
+    cs.largest = max(cs.elems(b) for b in cs.shapes)
+    last = {}
+    for idx, st in enumerate(cs.steps):
+        for b in st.reads():
+            last[b] = idx
+    last.update((b, len(cs.steps)) for b in keep)
+    live = set()
+    for idx, st in enumerate(cs.steps):
+        live.update(st.writes())
+        cs.peak = max(cs.peak, sum(cs.elems(b) for b in live))
+        st.free = sorted((b for b in live if last.get(b, -1) <= idx), key=key)
+        live.difference_update(st.free)
+
+
+# op kind -> the rule it breaks downstream of a GlobalAvgPool (its result is not pooled)
+POOL_RULES = {"relu": POOL_RULE_NONLIN, "erf": POOL_RULE_NONLIN, "gelu": GELU_RULE_GLOBAL,
+              "avgpool": AVGPOOL_RULE_GLOBAL, "corrconv": CORRCONV_RULE_GLOBAL}
+
+
+def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
     """The launches of a program with a GlobalAvgPool, an AvgPool2d or a CorrelatedConv2d
     (which stands where an AvgPool2d may, and marks ``avgpooled`` like one), over the program
     fused with rules 1 and 2 (conv with a ReLU post-stage, a two-term Sum as an addend).
@@ -551,13 +606,9 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
             avgpooled[op.dst] = any(avgpooled[t] for _, t in op.terms)
         else:
             avgpooled[op.dst] = op.kind in ("avgpool", "corrconv") or avgpooled[op.src]
-        if op.kind in ("relu", "erf"):
+        if op.kind in POOL_RULES:
             if pooled[op.src]:
-                raise NotImplementedError(POOL_RULE_NONLIN)
-            pooled[op.dst] = False
-        elif op.kind == "gelu":
-            if pooled[op.src]:
-                raise NotImplementedError(GELU_RULE_GLOBAL)
+                raise NotImplementedError(POOL_RULES[op.kind])
             pooled[op.dst] = False
         elif op.kind == "pool":
             if body:
@@ -566,14 +617,6 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
             if pooled[op.src]:
                 raise NotImplementedError(POOL_RULE_ONE)
             pooled[op.dst] = True
-        elif op.kind == "avgpool":
-            if pooled[op.src]:
-                raise NotImplementedError(AVGPOOL_RULE_GLOBAL)
-            pooled[op.dst] = False
-        elif op.kind == "corrconv":
-            if pooled[op.src]:
-                raise NotImplementedError(CORRCONV_RULE_GLOBAL)
-            pooled[op.dst] = False
         elif op.kind == "conv":
             if pooled[op.src] and tuple(op.shape_out) != (1, 1):
                 raise NotImplementedError(POOL_RULE_CONV)
@@ -588,51 +631,42 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> PoolSteps
     if not body and not pooled[vf]:
         raise NotImplementedError(POOL_RULE_ONE)
 
-    steps = [PoolStep("moments", v0)]
+    steps = [CovStep("moments", v0)]
     for op in fuse(prog, v0, vf, True, pre_relu=False, fold_moments=False):
         if op.kind == "conv" and op.post == N.CGP_POST_RELU and avgpooled[op.post_var]:
-            steps.append(PoolStep("conv", op.post_var, src=op.src, op=op))
-            steps.append(PoolStep("nonlin", op.dst, src=op.post_var, op=op, post=N.CGP_COV_RELU,
-                                  var=op.post_var, addend=op.addend))
+            steps.append(CovStep("conv", op.post_var, src=op.src, op=op, bias=op.geom.bias))
+            steps.append(CovStep("nonlin", op.dst, src=op.post_var, op=op, post=N.CGP_COV_RELU,
+                                 var=op.post_var, addend=op.addend))
         elif op.kind == "conv":
             relu = op.post == N.CGP_POST_RELU
-            steps.append(PoolStep("conv", op.dst, src=op.src, op=op,
-                                  post=N.CGP_COV_RELU if relu else N.CGP_COV_NONE,
-                                  var=op.post_var if relu else None, addend=op.addend))
+            steps.append(CovStep("conv", op.dst, src=op.src, op=op,
+                                 post=N.CGP_COV_RELU if relu else N.CGP_COV_NONE,
+                                 var=op.post_var if relu else None, addend=op.addend,
+                                 bias=op.geom.bias))
         elif op.kind in ("relu", "erf"):
-            steps.append(PoolStep("nonlin", op.dst, src=op.src, op=op,
-                                  post=N.CGP_COV_RELU if op.kind == "relu" else N.CGP_COV_ERF,
-                                  var=op.src, addend=op.addend))
+            steps.append(CovStep("nonlin", op.dst, src=op.src, op=op,
+                                 post=N.CGP_COV_RELU if op.kind == "relu" else N.CGP_COV_ERF,
+                                 var=op.src, addend=op.addend))
         elif op.kind == "gelu":
-            steps.append(PoolStep("gelu", op.dst, src=op.src, op=op, var=op.src,
-                                  addend=op.addend))
-        elif op.kind == "pool":
-            steps.append(PoolStep("pool", op.dst, src=op.src, op=op))
-        elif op.kind in ("avgpool", "corrconv"):
-            steps.append(PoolStep(op.kind, op.dst, src=op.src, op=op))
+            steps.append(CovStep("gelu", op.dst, src=op.src, op=op, var=op.src,
+                                 addend=op.addend))
+        elif op.kind in ("pool", "avgpool"):
+            steps.append(CovStep(op.kind, op.dst, src=op.src, op=op))
+        elif op.kind == "corrconv":
+            steps.append(CovStep("corrconv", op.dst, src=op.src, op=op, bias=op.geom.bias))
         else:
-            steps.append(PoolStep("axpby", op.dst, op=op, terms=list(op.terms)))
-    last = {}
-    for idx, st in enumerate(steps):
-        for b in st.reads():
-            last[b] = idx
-    last[vf] = len(steps)
+            steps.append(CovStep("axpby", op.dst, op=op, terms=list(op.terms)))
     bufs = [st.dst for st in steps]
-    ps = PoolSteps(steps, {b: prog.shapes[b] for b in bufs},
-                   frozenset(b for b in bufs if not pooled[b]),
-                   frozenset(b for b in bufs if pooled[b]),
-                   frozenset(v for v, p in pooled.items() if p), vf,
-                   frozenset(st.var for st in steps if st.var is not None), 0,
-                   frozenset(v for v, a in avgpooled.items() if a))
+    ps = CovSteps(steps, {b: prog.shapes[b] for b in bufs},
+                  frozenset(b for b in bufs if not pooled[b]),
+                  frozenset(b for b in bufs if pooled[b]), vf,
+                  frozenset(st.var for st in steps if st.var is not None),
+                  pooled=frozenset(v for v, p in pooled.items() if p),
+                  avgpooled=frozenset(v for v, a in avgpooled.items() if a))
     ps.self_var = frozenset(v for v in ps.need_var if avgpooled[v])
     ps.self_last = max((idx for idx, st in enumerate(steps) if st.dst in ps.self_var),
                        default=-1)
-    live = set()
-    for idx, st in enumerate(steps):
-        live.add(st.dst)
-        ps.peak = max(ps.peak, sum(ps.elems(b) for b in live))
-        st.free = sorted(b for b in live if last.get(b, -1) <= idx)
-        live.difference_update(st.free)
+    _schedule(ps, [vf])
     return ps
 
 
@@ -650,71 +684,8 @@ def conv_ntk_fits(taps: int, w: int, streams: int, itemsize: int) -> bool:
     return unit + 8 <= COV_NTK_MAX_LDS and taps <= 1024
 
 
-@dataclasses.dataclass
-class PoolNtkStep:
-    """One launch of a pooled NTK run.  Buffers are named ("K", v) / ("T", v), the K and Θ
-    position-pair maps of an SSA value, as in ntk_steps; v is ("pre", d) for the conv
-    output that a fused addend replaced in the forward program.
-
-    The forward launches of PoolStep, on either stream (fn "moments", "conv", "nonlin", "gelu",
-    "pool", "avgpool", "corrconv", "axpby"; ``bias`` replaces a conv geometry's: 0 on the Θ
-    stream), and
-    fn "conv_ntk":   dst, dst_theta = the two-stream conv of (src, theta), theta None for
-                     Θ = 0, [→ nonlinearity ``post``] [+ addend, + addend_theta]
-                                                                          cgp_covntk_conv_*
-    fn "nonlin_ntk": dst, dst_theta = ``post`` of src [+ addend], theta·κ̇ [+ addend_theta]
-                                                                          cgp_covntk_nonlin_*
-    fn "accum":      dst = dst + src, in place                            cgp_axpby_*
-    ``free``: the buffers nothing reads after this launch."""
-    fn: str
-    dst: tuple
-    src: Optional[tuple] = None
-    op: Optional[Op] = None
-    post: int = N.CGP_COV_NONE
-    var: Optional[int] = None
-    addend: Optional[tuple] = None
-    bias: Optional[float] = None
-    theta: Optional[tuple] = None
-    dst_theta: Optional[tuple] = None
-    addend_theta: Optional[tuple] = None
-    terms: list = dataclasses.field(default_factory=list)
-    free: list = dataclasses.field(default_factory=list)
-
-    def reads(self):
-        r = [b for b in (self.src, self.addend, self.theta, self.addend_theta)
-             if b is not None]
-        if self.fn == "accum":
-            r.append(self.dst)
-        return r + [b for _, b in self.terms]
-
-    def writes(self):
-        return [b for b in (self.dst, self.dst_theta) if b is not None]
-
-
-@dataclasses.dataclass
-class PoolNtkSteps:
-    """pool_ntk_steps' result: PoolSteps' fields over the buffers of both streams, plus
-    ``final_theta`` (the buffer that holds Θ of the final value: ``final`` itself after a
-    single conv, None for Θ = 0) and ``forward``, the forward-only PoolSteps of the same
-    program (its self pass gives the variances downstream of an AvgPool2d)."""
-    steps: list
-    shapes: dict
-    maps: frozenset
-    scalars: frozenset
-    final: tuple
-    final_theta: Optional[tuple]
-    need_var: frozenset
-    peak: int
-    forward: PoolSteps
-    fused: bool = True
-
-    def elems(self, b) -> int:
-        h, w = self.shapes[b]
-        return (h * w) ** 2 if b in self.maps else 1
-
-
 def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: bool = True,
-                   itemsize: int = 8) -> PoolNtkSteps:
+                   itemsize: int = 8) -> CovSteps:
     """The launches that carry (K, Θ) through a program on position-pair maps: the two-stream
     counterpart of pool_steps, over the same fused program and with the same rejections.
 
@@ -758,70 +729,70 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
         ta = theta.get(st.addend) if st.addend is not None else None
         ka = K(st.addend) if st.addend is not None else None
         if st.fn == "moments":
-            emit(PoolNtkStep("moments", K(d)), shape, sc)
+            emit(CovStep("moments", K(d)), shape, sc)
         elif st.fn == "conv":
             g = op.geom
             plain = st.post == N.CGP_COV_NONE and st.addend is None
             if plain and ts is None:
-                emit(PoolNtkStep("conv", K(d), src=K(st.src), op=op, bias=g.bias), shape, sc)
+                emit(CovStep("conv", K(d), src=K(st.src), op=op, bias=g.bias), shape, sc)
                 theta[d] = K(d)
             elif fused and conv_ntk_fits(g.taps, fwd.shapes[st.src][1],
                                          1 if ts is None else 2, itemsize):
-                emit(PoolNtkStep("conv_ntk", K(d), src=K(st.src), op=op, post=st.post,
-                                 var=st.var, addend=ka, bias=g.bias, theta=ts,
-                                 dst_theta=("T", d), addend_theta=ta), shape, sc)
+                emit(CovStep("conv_ntk", K(d), src=K(st.src), op=op, post=st.post,
+                             var=st.var, addend=ka, bias=g.bias, theta=ts,
+                             dst_theta=("T", d), addend_theta=ta), shape, sc)
                 theta[d] = ("T", d)
             else:
                 pre = d if plain else (st.var if st.post != N.CGP_COV_NONE else ("pre", d))
-                emit(PoolNtkStep("conv", K(pre), src=K(st.src), op=op, bias=g.bias), shape, sc)
+                emit(CovStep("conv", K(pre), src=K(st.src), op=op, bias=g.bias), shape, sc)
                 tpre = K(pre)
                 if ts is not None:
                     tpre = ("T", pre)
-                    emit(PoolNtkStep("conv", tpre, src=ts, op=op, bias=0.0, addend=K(pre)),
+                    emit(CovStep("conv", tpre, src=ts, op=op, bias=0.0, addend=K(pre)),
                          shape, sc)
                 if plain:
                     theta[d] = tpre
                 elif st.post != N.CGP_COV_NONE:
-                    emit(PoolNtkStep("nonlin_ntk", K(d), src=K(pre), op=op, post=st.post,
-                                     var=st.var, addend=ka, theta=tpre, dst_theta=("T", d),
-                                     addend_theta=ta), shape, sc)
+                    emit(CovStep("nonlin_ntk", K(d), src=K(pre), op=op, post=st.post,
+                                 var=st.var, addend=ka, theta=tpre, dst_theta=("T", d),
+                                 addend_theta=ta), shape, sc)
                     theta[d] = ("T", d)
                 else:
-                    emit(PoolNtkStep("axpby", K(d), op=op, terms=[(None, K(pre)), (None, ka)]),
+                    emit(CovStep("axpby", K(d), op=op, terms=[(None, K(pre)), (None, ka)]),
                          shape, sc)
                     if ta is None:
                         theta[d] = tpre
                     else:
-                        emit(PoolNtkStep("axpby", ("T", d), op=op,
-                                         terms=[(None, tpre), (None, ta)]), shape, sc)
+                        emit(CovStep("axpby", ("T", d), op=op,
+                                     terms=[(None, tpre), (None, ta)]), shape, sc)
                         theta[d] = ("T", d)
         elif st.fn in ("nonlin", "gelu"):
             if ts is None:
-                emit(PoolNtkStep(st.fn, K(d), src=K(st.src), op=op, post=st.post, var=st.var,
-                                 addend=ka), shape, sc)
+                emit(CovStep(st.fn, K(d), src=K(st.src), op=op, post=st.post, var=st.var,
+                             addend=ka), shape, sc)
                 theta[d] = ta
             else:
-                emit(PoolNtkStep("nonlin_ntk", K(d), src=K(st.src), op=op,
-                                 post=N.CGP_COV_GELU if st.fn == "gelu" else st.post,
-                                 var=st.var, addend=ka, theta=ts, dst_theta=("T", d),
-                                 addend_theta=ta), shape, sc)
+                emit(CovStep("nonlin_ntk", K(d), src=K(st.src), op=op,
+                             post=N.CGP_COV_GELU if st.fn == "gelu" else st.post,
+                             var=st.var, addend=ka, theta=ts, dst_theta=("T", d),
+                             addend_theta=ta), shape, sc)
                 theta[d] = ("T", d)
         elif st.fn in ("pool", "avgpool"):
-            emit(PoolNtkStep(st.fn, K(d), src=K(st.src), op=op), shape, sc)
+            emit(CovStep(st.fn, K(d), src=K(st.src), op=op), shape, sc)
             theta[d] = None
             if ts is not None:
-                emit(PoolNtkStep(st.fn, ("T", d), src=ts, op=op), shape, sc)
+                emit(CovStep(st.fn, ("T", d), src=ts, op=op), shape, sc)
                 theta[d] = ("T", d)
         elif st.fn == "corrconv":
-            emit(PoolNtkStep("corrconv", K(d), src=K(st.src), op=op, bias=op.geom.bias),
+            emit(CovStep("corrconv", K(d), src=K(st.src), op=op, bias=op.geom.bias),
                  shape, sc)
             theta[d] = K(d)
             if ts is not None:
-                emit(PoolNtkStep("corrconv", ("T", d), src=ts, op=op, bias=0.0), shape, sc)
-                emit(PoolNtkStep("accum", ("T", d), src=K(d), op=op), shape, sc)
+                emit(CovStep("corrconv", ("T", d), src=ts, op=op, bias=0.0), shape, sc)
+                emit(CovStep("accum", ("T", d), src=K(d), op=op), shape, sc)
                 theta[d] = ("T", d)
         elif st.fn == "axpby":
-            emit(PoolNtkStep("axpby", K(d), op=op, terms=[(c, K(t)) for c, t in st.terms]),
+            emit(CovStep("axpby", K(d), op=op, terms=[(c, K(t)) for c, t in st.terms]),
                  shape, sc)
             live = [(c, theta[t]) for c, t in st.terms if theta[t] is not None]
             if not live:
@@ -829,27 +800,15 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
             elif len(live) == 1 and live[0][0] is None:
                 theta[d] = live[0][1]
             else:
-                emit(PoolNtkStep("axpby", ("T", d), op=op, terms=live), shape, sc)
+                emit(CovStep("axpby", ("T", d), op=op, terms=live), shape, sc)
                 theta[d] = ("T", d)
         else:
             raise AssertionError(st.fn)
 
-    last = {}
-    for idx, st in enumerate(steps):
-        for b in st.reads():
-            last[b] = idx
-    final, final_theta = K(vf), theta[vf]
-    last[final] = len(steps)
-    if final_theta is not None:
-        last[final_theta] = len(steps)
-    ns = PoolNtkSteps(steps, shapes, frozenset(b for b in shapes if b not in scalars),
-                      frozenset(scalars), final, final_theta, fwd.need_var, 0, fwd, fused)
-    live = set()
-    for idx, st in enumerate(steps):
-        live.update(st.writes())
-        ns.peak = max(ns.peak, sum(ns.elems(b) for b in live))
-        st.free = sorted((b for b in live if last.get(b, -1) <= idx), key=repr)
-        live.difference_update(st.free)
+    ns = CovSteps(steps, shapes, frozenset(b for b in shapes if b not in scalars),
+                  frozenset(scalars), K(vf), fwd.need_var, final_theta=theta[vf], forward=fwd,
+                  fused=fused)
+    _schedule(ns, [b for b in (ns.final, ns.final_theta) if b is not None], key=repr)
     return ns
 
 
@@ -861,6 +820,16 @@ def _adjacent(x, y) -> bool:
     return (x.is_contiguous() and y.is_contiguous() and x.dtype == y.dtype
             and y.data_ptr() == x.data_ptr() + x.numel() * x.element_size())
 
+
+def _axpby_terms(sfx, terms, out, n, stream):
+    """out[:n] = Σ coef·tensor over ``terms`` (coef None: 1), one cgp_axpby_* launch per term:
+    the first term overwrites, later terms accumulate."""
+    for k, (coef, src) in enumerate(terms):
+        c = 1.0 if coef is None else coef
+        if k == 0:
+            N.call(f"cgp_axpby_{sfx}", c, N.ptr(src), 0.0, None, N.ptr(out), n, stream)
+        else:
+            N.call(f"cgp_axpby_{sfx}", 1.0, N.ptr(out), c, N.ptr(src), N.ptr(out), n, stream)
 
 
 class DevPtr:
@@ -888,7 +857,7 @@ class Plan:
         self.final_hw = (fh, fw)
         self.moments_fused = any(o.pre == N.CGP_PRE_MOMENTS for o in self.pair_ops)
         # a model with a GlobalAvgPool, an AvgPool2d or a CorrelatedConv2d runs on
-        # position-pair maps (run_pairs_pool); its rejections are raised here, when the program
+        # position-pair maps (run_cov_steps); its rejections are raised here, when the program
         # is compiled.  Without a GlobalAvgPool the final value is a map (1x1 for forward)
         kinds = {o.kind for o in self.prog.ops}
         self.pool = pool_steps(self.prog, self.v0, self.vf, body="pool" not in kinds) \
@@ -966,18 +935,8 @@ class Plan:
                 whole = all(_adjacent(*vals[t]) for _, t in op.terms)
                 for part, o, n in (((None, buf, n1 + n2),) if whole else
                                    ((0, outx, n1), (1, outy, n2))):
-                    first = True
-                    for coef, t in op.terms:
-                        src = vals[t][0] if part is None else vals[t][part]
-                        if first:
-                            alpha = 1.0 if coef is None else coef
-                            N.call(f"cgp_axpby_{sfx}", alpha, N.ptr(src), 0.0, None, N.ptr(o),
-                                   n * ho * wo, stream)
-                            first = False
-                        else:
-                            beta = 1.0 if coef is None else coef
-                            N.call(f"cgp_axpby_{sfx}", 1.0, N.ptr(o), beta, N.ptr(src), N.ptr(o),
-                                   n * ho * wo, stream)
+                    _axpby_terms(sfx, [(coef, vals[t][part or 0]) for coef, t in op.terms], o,
+                                 n * ho * wo, stream)
                 out = (outx, outy)
             else:
                 raise AssertionError(op.kind)
@@ -1212,14 +1171,7 @@ class Plan:
                 srcs = [(coef, vals[t]) for coef, t in op.terms]
 
                 def launch(srcs=srcs, out=out, n=n):
-                    for k, (coef, src) in enumerate(srcs):
-                        c = 1.0 if coef is None else coef
-                        if k == 0:
-                            N.call(f"cgp_axpby_{sfx}", c, N.ptr(src), 0.0, None, N.ptr(out), n,
-                                   stream)
-                        else:
-                            N.call(f"cgp_axpby_{sfx}", 1.0, N.ptr(out), c, N.ptr(src),
-                                   N.ptr(out), n, stream)
+                    _axpby_terms(sfx, srcs, out, n, stream)
             else:
                 raise AssertionError(op.kind)
             launch()
@@ -1319,15 +1271,8 @@ class Plan:
                 N.check(getattr(lib, f"cgp_{op.kind}_{sfx}")(r, stream), "cgp_" + op.kind)
             elif st.fn == "axpby":
                 out = bufs[st.dst] = new(op)
-                n = nmaps * ho * wo
-                for k, (coef, b) in enumerate(st.terms):
-                    c = 1.0 if coef is None else coef
-                    if k == 0:
-                        N.call(f"cgp_axpby_{sfx}", c, N.ptr(bufs[b]), 0.0, None, N.ptr(out), n,
-                               stream)
-                    else:
-                        N.call(f"cgp_axpby_{sfx}", 1.0, N.ptr(out), c, N.ptr(bufs[b]),
-                               N.ptr(out), n, stream)
+                _axpby_terms(sfx, [(c, bufs[b]) for c, b in st.terms], out, nmaps * ho * wo,
+                             stream)
             else:
                 raise AssertionError(st.fn)
             for b in [b for b in bufs if last.get(b, -1) <= idx and b not in st.writes()]:
@@ -1335,7 +1280,7 @@ class Plan:
         return bufs[kbuf], (None if tbuf is None else bufs[tbuf])
 
     # -- GlobalAvgPool: the program on position-pair maps ---------------------------------
-    def body_steps(self) -> PoolSteps:
+    def body_steps(self) -> CovSteps:
         """pool_steps of a model without a pool (position_covariance): the final value is
         the position-pair map a GlobalAvgPool after the model would read."""
         if "_body_steps" not in self.__dict__:
@@ -1356,7 +1301,7 @@ class Plan:
             cache[key] = tabs
         return tabs
 
-    def pool_ntk(self, body: bool, fused: bool, itemsize: int) -> PoolNtkSteps:
+    def pool_ntk(self, body: bool, fused: bool, itemsize: int) -> CovSteps:
         """pool_ntk_steps of the plan's program, cached per (body, fused, itemsize)."""
         cache = self.__dict__.setdefault("_pool_ntk", {})
         key = (bool(body), bool(fused), int(itemsize))
@@ -1365,153 +1310,12 @@ class Plan:
                                         itemsize=itemsize)
         return cache[key]
 
-    def run_pairs_pool_ntk(self, x, y, var, pair_i, pair_j, same, stream, ns, max_bytes=None):
-        """Runs ``ns`` (pool_ntk_steps) over the pairs (pair_i[m], pair_j[m]) -- device int32
-        arrays -- in chunks of pairs, like run_pairs_pool; returns (K, Θ) of the final value
-        of every pair as [npairs, elements] tensors, Θ None when it is zero (a model without
-        a conv).  var: the variance maps of ns.need_var (run_variances, and run_self_variances
-        on ns.forward for the values downstream of an AvgPool2d).  A chunk takes ns.peak
-        elements per pair, both streams counted; the result does not depend on the
-        chunking."""
-        sfx = self._sfx(x.dtype)
-        lib = N.load()
-        dev = x.device
-        item = x.element_size()
-        npairs = pair_i.numel()
-        if max_bytes is None:
-            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
-        per_pair = ns.peak * item
-        chunk = int(max_bytes) // per_pair
-        if chunk < 1:
-            big = max(ns.elems(b) for b in ns.shapes)
-            raise RuntimeError(
-                f"ntk_maps: one image pair needs {per_pair} bytes of position-pair maps "
-                f"({ns.peak} live elements of {item} bytes at the fullest launch, K and Θ; the "
-                f"largest map holds {big}), more than the workspace of {int(max_bytes)} bytes "
-                "(set_pool_workspace)")
-        chunk = min(chunk, npairs, max(1, (1 << 40) // max(ns.elems(b) for b in ns.shapes)))
-        C = x.shape[1]
-        out_k = torch.empty((npairs, ns.elems(ns.final)), dtype=x.dtype, device=dev)
-        out_t = None
-        if ns.final_theta is not None and ns.final_theta != ns.final:
-            out_t = torch.empty_like(out_k)
-        axpby = f"cgp_axpby_{sfx}"
-        for a in range(0, npairs, chunk):
-            n = min(chunk, npairs - a)
-            pi, pj = pair_i[a:a + n], pair_j[a:a + n]
-            bufs = {}
-
-            def new(b):
-                if b in bufs:                          # fn "accum" writes in place
-                    return bufs[b]
-                if b == ns.final:
-                    bufs[b] = out_k[a:a + n]
-                elif out_t is not None and b == ns.final_theta:
-                    bufs[b] = out_t[a:a + n]
-                else:
-                    bufs[b] = torch.empty((n, ns.elems(b)), dtype=x.dtype, device=dev)
-                return bufs[b]
-
-            def get(b):
-                return None if b is None else N.ptr(bufs[b])
-
-            for st in ns.steps:
-                h, w = ns.shapes[st.dst]
-                ne = ns.elems(st.dst)
-                dst = new(st.dst)
-                if st.fn == "moments":
-                    N.check(getattr(lib, f"cgp_cov_moments_{sfx}")(
-                        N.ptr(x), N.ptr(y), N.ptr(pi), N.ptr(pj), n, C, h, w, N.ptr(dst),
-                        stream), "cgp_cov_moments")
-                elif st.fn in ("conv", "conv_ntk"):
-                    g = st.op.geom
-                    ntk = st.fn == "conv_ntk"
-                    r = N.CovConvNtkArgs() if ntk else N.CovConvArgs()
-                    r.in_, r.out, r.addend = get(st.src), N.ptr(dst), get(st.addend)
-                    if ntk:
-                        r.theta, r.out_theta = get(st.theta), N.ptr(new(st.dst_theta))
-                        r.addend_theta = get(st.addend_theta)
-                    if st.var is not None:
-                        vx, vy = var[st.var]
-                        r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
-                    (r.h, r.w), r.ho, r.wo = ns.shapes[st.src], h, w
-                    r.taps, r.offset, r.stride, r.dilation = g.taps, g.offset, g.stride, \
-                        g.dilation
-                    r.post, r.same, r.flags = st.post, int(same), self.flags
-                    r.weight, r.bias = g.weight, st.bias
-                    what = "cgp_covntk_conv" if ntk else "cgp_cov_conv"
-                    N.check(getattr(lib, f"{what}_{sfx}")(r, stream), what)
-                elif st.fn == "nonlin_ntk":
-                    vx, vy = var[st.var]
-                    r = N.CovNonlinNtkArgs()
-                    r.in_, r.theta, r.out = get(st.src), get(st.theta), N.ptr(dst)
-                    r.out_theta = N.ptr(new(st.dst_theta))
-                    r.addend, r.addend_theta = get(st.addend), get(st.addend_theta)
-                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
-                    r.h, r.w, r.kind, r.same, r.flags = h, w, st.post, int(same), self.flags
-                    N.check(getattr(lib, f"cgp_covntk_nonlin_{sfx}")(r, stream),
-                            "cgp_covntk_nonlin")
-                elif st.fn == "nonlin":
-                    vx, vy = var[st.var]
-                    r = N.CovNonlinArgs()
-                    r.in_, r.out, r.addend = get(st.src), N.ptr(dst), get(st.addend)
-                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
-                    r.h, r.w, r.kind, r.same, r.flags = h, w, st.post, int(same), self.flags
-                    N.check(getattr(lib, f"cgp_cov_nonlin_{sfx}")(r, stream), "cgp_cov_nonlin")
-                elif st.fn == "gelu":
-                    vx, vy = var[st.var]
-                    r = N.GeluCovArgs()
-                    r.in_, r.out, r.addend = get(st.src), N.ptr(dst), get(st.addend)
-                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
-                    r.h, r.w, r.same = h, w, int(same)
-                    N.check(getattr(lib, f"cgp_gelu_cov_{sfx}")(r, stream), "cgp_gelu_cov")
-                elif st.fn == "pool":
-                    N.check(getattr(lib, f"cgp_cov_pool_{sfx}")(
-                        get(st.src), n, ns.elems(st.src), N.ptr(dst), stream), "cgp_cov_pool")
-                elif st.fn == "avgpool":
-                    r = N.CovAvgPoolArgs()
-                    r.in_, r.out, r.npairs = get(st.src), N.ptr(dst), n
-                    (r.h, r.w), r.ho, r.wo = ns.shapes[st.src], h, w
-                    r.k, r.stride = st.op.geom.taps, st.op.geom.stride
-                    N.check(getattr(lib, f"cgp_covmap_avgpool_{sfx}")(r, stream),
-                            "cgp_covmap_avgpool")
-                elif st.fn == "corrconv":
-                    g = st.op.geom
-                    rr, rc = self._corr_tables(st.op, dev, x.dtype)
-                    r = N.CorrConvArgs()
-                    r.in_, r.out, r.npairs = get(st.src), N.ptr(dst), n
-                    r.corr_rows, r.corr_cols = N.ptr(rr), N.ptr(rc)
-                    (r.h, r.w), r.ho, r.wo = ns.shapes[st.src], h, w
-                    r.taps, r.offset, r.stride, r.dilation = g.taps, g.offset, g.stride, g.dilation
-                    r.weight, r.bias = g.weight, st.bias
-                    N.check(getattr(lib, f"cgp_corrconv_{sfx}")(r, stream), "cgp_corrconv")
-                elif st.fn == "accum":
-                    N.call(axpby, 1.0, N.ptr(dst), 1.0, get(st.src), N.ptr(dst), n * ne, stream)
-                elif st.fn == "axpby":
-                    for k, (coef, b) in enumerate(st.terms):
-                        c = 1.0 if coef is None else coef
-                        if k == 0:
-                            N.call(axpby, c, get(b), 0.0, None, N.ptr(dst), n * ne, stream)
-                        else:
-                            N.call(axpby, 1.0, N.ptr(dst), c, get(b), N.ptr(dst), n * ne, stream)
-                else:
-                    raise AssertionError(st.fn)
-                for b in st.free:
-                    del bufs[b]
-        if ns.final_theta == ns.final:
-            out_t = out_k.clone()
-        return out_k, out_t
-
     def run_self_variances(self, x, var, stream, ps=None, max_bytes=None, want=None):
         """The variance maps [n, h, w] of the values ``want`` (default ps.self_var: what the
         nonlinearities downstream of an AvgPool2d read) of the images x: the p = q diagonals
         of the values' position-pair maps on the self pairs (i, i), run with ``same`` so the
         nonlinearities' override applies there.  The launches are ps.steps up to the last one
-        that writes a wanted value, chunked like run_pairs_pool; a nonlinearity inside reads
+        that writes a wanted value, chunked by run_cov_steps; a nonlinearity inside reads
         the diagonal just extracted from its own source.  var: value -> [n, h, w] maps of the
         values upstream of every AvgPool2d (one side of run_variances' pairs).  A wanted
         value must be a buffer of ps (the destination of a launch)."""
@@ -1527,26 +1331,27 @@ class Plan:
         both = {v: (m, m) for v, m in var.items()}
         both.update({v: (m, m) for v, m in out.items()})
         idx = torch.arange(n, device=x.device, dtype=torch.int32)
-        self.run_pairs_pool(x, x, both, idx, idx, True, stream, ps, max_bytes, last=last,
-                            diag_out=out)
+        self.run_cov_steps(ps, x, x, both, idx, idx, True, stream, max_bytes, last=last,
+                           diag_out=out)
         return {v: out[v] for v in want}
 
-    def run_pairs_pool(self, x, y, var, pair_i, pair_j, same, stream, ps=None,
-                       max_bytes=None, last=None, diag_out=None):
-        """Runs ``ps`` (default: the plan's own pool_steps) over the pairs (pair_i[m],
-        pair_j[m]) -- device int32 arrays -- in chunks of pairs; returns the final value of
-        every pair as [npairs, elements] (one element per pair after a pool).
-        x, y: images [n, C, H, W]; var: the variance maps of ps.need_var (run_variances, and
-        run_self_variances for ps.self_var).  ``last``: run ps.steps[:last + 1] only and
-        return nothing; ``diag_out``: value -> [n, h, w] tensor that takes the p = q diagonal
-        of the value's map of pair m at image pair_i[m] (cgp_covmap_diag_*), right after the
-        launch that writes it.
+    def run_cov_steps(self, cs, x, y, var, pair_i, pair_j, same, stream, max_bytes=None,
+                      last=None, diag_out=None):
+        """Runs the launch list ``cs`` (pool_steps or pool_ntk_steps) over the pairs
+        (pair_i[m], pair_j[m]) -- device int32 arrays -- in chunks of pairs; returns (K, Θ) of
+        the final value of every pair as [npairs, elements] tensors (one element per pair
+        after a pool), Θ None for a forward list and where it is zero (a model without a conv).
+        x, y: images [n, C, H, W]; var: the variance maps of cs.need_var (run_variances, and
+        run_self_variances on the forward list for its self_var).  ``last``: run
+        cs.steps[:last + 1] only and return nothing; ``diag_out``: value -> [n, h, w] tensor
+        that takes the p = q diagonal of the value's map of pair m at image pair_i[m]
+        (cgp_covmap_diag_*), right after the launch that writes it.
 
-        A chunk takes ps.peak elements per pair at its fullest launch (every buffer is freed
-        after its last reader); chunks are sized to stay under ``max_bytes`` (default: a
-        quarter of the device's free memory).  Each kernel computes a pair from that pair's
-        data alone in a fixed order, so the result does not depend on the chunking."""
-        ps = self.pool if ps is None else ps
+        A chunk takes cs.peak elements per pair at its fullest launch, both streams counted
+        (every buffer is freed after its last reader); chunks are sized to stay under
+        ``max_bytes`` (default: a quarter of the device's free memory).  Each kernel computes a
+        pair from that pair's data alone in a fixed order, so the result does not depend on the
+        chunking."""
         sfx = self._sfx(x.dtype)
         lib = N.load()
         dev = x.device
@@ -1554,105 +1359,114 @@ class Plan:
         npairs = pair_i.numel()
         if max_bytes is None:
             max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
-        per_pair = ps.peak * item
+        per_pair = cs.peak * item
         chunk = int(max_bytes) // per_pair
         if chunk < 1:
-            big = max(ps.elems(b) for b in ps.shapes)
+            what, both = ("ntk_maps", ", K and Θ") if cs.forward is not None else \
+                ("GlobalAvgPool", "")
             raise RuntimeError(
-                f"GlobalAvgPool: one image pair needs {per_pair} bytes of position-pair maps "
-                f"({ps.peak} live elements of {item} bytes at the fullest launch; the largest "
-                f"map holds {big}), more than the workspace of {int(max_bytes)} bytes "
+                f"{what}: one image pair needs {per_pair} bytes of position-pair maps "
+                f"({cs.peak} live elements of {item} bytes at the fullest launch{both}; the "
+                f"largest map holds {cs.largest}), more than the workspace of {int(max_bytes)} bytes "
                 "(set_pool_workspace)")
         # pairs·elements of one launch stay below 2^40 (the entry points count blocks in int32)
-        chunk = min(chunk, npairs, max(1, (1 << 40) // max(ps.elems(b) for b in ps.shapes)))
+        chunk = min(chunk, npairs, max(1, (1 << 40) // cs.largest))
         C = x.shape[1]
-        steps = ps.steps if last is None else ps.steps[:last + 1]
+        steps = cs.steps if last is None else cs.steps[:last + 1]
         diag_out = diag_out or {}
-        out = None if last is not None else \
-            torch.empty((npairs, ps.elems(ps.final)), dtype=x.dtype, device=dev)
+        outs = {}                               # the final buffers are slices of the output
+        if last is None:
+            outs[cs.final] = torch.empty((npairs, cs.elems(cs.final)), dtype=x.dtype, device=dev)
+            if cs.final_theta not in (None, cs.final):
+                outs[cs.final_theta] = torch.empty_like(outs[cs.final])
+        # device pointers are taken once per buffer, not once per use
+        xp, yp, flags, same = N.ptr(x), N.ptr(y), self.flags, int(same)
+        vptr = {v: (N.ptr(vx), N.ptr(vy)) for v, (vx, vy) in var.items()}
+
+        def new(b):
+            if b not in bufs:                          # fn "accum" writes in place
+                bufs[b] = outs[b][a:a + n] if b in outs else \
+                    torch.empty((n, cs.elems(b)), dtype=x.dtype, device=dev)
+                ptr[b] = N.ptr(bufs[b])
+            return ptr[b]
+
+        def maps(r, st):
+            """the fields every argument struct has: the maps in and out"""
+            r.in_, r.out, r.npairs = ptr[st.src], ptr[st.dst], n
+            r.h, r.w = cs.shapes[st.src]
+            return r
+
+        def stencil(r, st):
+            """a conv's or corrconv's output size, taps, weight and the step's bias"""
+            g = st.op.geom
+            r.ho, r.wo = cs.shapes[st.dst]
+            r.taps, r.offset, r.stride, r.dilation = g.taps, g.offset, g.stride, g.dilation
+            r.weight, r.bias = g.weight, st.bias
+            return r
+
+        def pairwise(r, st):
+            """the fields of the kernels that know the pair: its images' variances (only where
+            a nonlinearity reads them), the addend and the second stream"""
+            if st.var is not None:
+                r.xx, r.yy = vptr[st.var]
+            r.pair_i, r.pair_j, r.same, r.addend = pi, pj, same, ptr[st.addend]
+            if st.dst_theta is not None:
+                r.theta, r.out_theta = ptr[st.theta], new(st.dst_theta)
+                r.addend_theta = ptr[st.addend_theta]
+            return r
+
         for a in range(0, npairs, chunk):
             n = min(chunk, npairs - a)
-            pi, pj = pair_i[a:a + n], pair_j[a:a + n]
-            bufs = {}
+            pi, pj = N.ptr(pair_i[a:a + n]), N.ptr(pair_j[a:a + n])
+            bufs, ptr = {}, {None: None}        # the live tensors; every buffer's pointer
             for st in steps:
-                h, w = ps.shapes[st.dst]
-                ne = ps.elems(st.dst)
-                dst = out[a:a + n] if out is not None and st.dst == ps.final else \
-                    torch.empty((n, ne), dtype=x.dtype, device=dev)
-                bufs[st.dst] = dst
+                h, w = cs.shapes[st.dst]
+                dst = new(st.dst)
+                ntk = st.dst_theta is not None
                 if st.fn == "moments":
                     N.check(getattr(lib, f"cgp_cov_moments_{sfx}")(
-                        N.ptr(x), N.ptr(y), N.ptr(pi), N.ptr(pj), n, C, h, w, N.ptr(dst),
-                        stream), "cgp_cov_moments")
-                elif st.fn == "conv":
-                    g = st.op.geom
-                    r = N.CovConvArgs()
-                    r.in_, r.out = N.ptr(bufs[st.src]), N.ptr(dst)
-                    r.addend = N.ptr(bufs[st.addend]) if st.addend is not None else None
-                    if st.var is not None:
-                        vx, vy = var[st.var]
-                        r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
-                    (r.h, r.w), r.ho, r.wo = ps.shapes[st.src], h, w
-                    r.taps, r.offset, r.stride, r.dilation = g.taps, g.offset, g.stride, \
-                        g.dilation
-                    r.post, r.same, r.flags = st.post, int(same), self.flags
-                    r.weight, r.bias = g.weight, g.bias
-                    N.check(getattr(lib, f"cgp_cov_conv_{sfx}")(r, stream), "cgp_cov_conv")
-                elif st.fn == "nonlin":
-                    vx, vy = var[st.var]
-                    r = N.CovNonlinArgs()
-                    r.in_, r.out = N.ptr(bufs[st.src]), N.ptr(dst)
-                    r.addend = N.ptr(bufs[st.addend]) if st.addend is not None else None
-                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
-                    r.h, r.w, r.kind, r.same, r.flags = h, w, st.post, int(same), self.flags
-                    N.check(getattr(lib, f"cgp_cov_nonlin_{sfx}")(r, stream), "cgp_cov_nonlin")
-                elif st.fn == "gelu":
-                    vx, vy = var[st.var]
-                    r = N.GeluCovArgs()
-                    r.in_, r.out = N.ptr(bufs[st.src]), N.ptr(dst)
-                    r.addend = N.ptr(bufs[st.addend]) if st.addend is not None else None
-                    r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                    r.pair_i, r.pair_j, r.npairs = N.ptr(pi), N.ptr(pj), n
-                    r.h, r.w, r.same = h, w, int(same)
-                    N.check(getattr(lib, f"cgp_gelu_cov_{sfx}")(r, stream), "cgp_gelu_cov")
+                        xp, yp, pi, pj, n, C, h, w, dst, stream), "cgp_cov_moments")
                 elif st.fn == "pool":
                     N.check(getattr(lib, f"cgp_cov_pool_{sfx}")(
-                        N.ptr(bufs[st.src]), n, ps.elems(st.src), N.ptr(dst), stream),
-                        "cgp_cov_pool")
-                elif st.fn == "avgpool":
-                    r = N.CovAvgPoolArgs()
-                    r.in_, r.out, r.npairs = N.ptr(bufs[st.src]), N.ptr(dst), n
-                    (r.h, r.w), r.ho, r.wo = ps.shapes[st.src], h, w
-                    r.k, r.stride = st.op.geom.taps, st.op.geom.stride
-                    N.check(getattr(lib, f"cgp_covmap_avgpool_{sfx}")(r, stream),
-                            "cgp_covmap_avgpool")
-                elif st.fn == "corrconv":
-                    g = st.op.geom
-                    rr, rc = self._corr_tables(st.op, dev, x.dtype)
-                    r = N.CorrConvArgs()
-                    r.in_, r.out, r.npairs = N.ptr(bufs[st.src]), N.ptr(dst), n
-                    r.corr_rows, r.corr_cols = N.ptr(rr), N.ptr(rc)
-                    (r.h, r.w), r.ho, r.wo = ps.shapes[st.src], h, w
-                    r.taps, r.offset, r.stride, r.dilation = g.taps, g.offset, g.stride, g.dilation
-                    r.weight, r.bias = g.weight, g.bias
-                    N.check(getattr(lib, f"cgp_corrconv_{sfx}")(r, stream), "cgp_corrconv")
+                        ptr[st.src], n, cs.elems(st.src), dst, stream), "cgp_cov_pool")
+                elif st.fn == "accum":
+                    N.call(f"cgp_axpby_{sfx}", 1.0, dst, 1.0, ptr[st.src], dst,
+                           n * cs.elems(st.dst), stream)
                 elif st.fn == "axpby":
-                    for k, (coef, b) in enumerate(st.terms):
-                        c = 1.0 if coef is None else coef
-                        if k == 0:
-                            N.call(f"cgp_axpby_{sfx}", c, N.ptr(bufs[b]), 0.0, None, N.ptr(dst),
-                                   n * ne, stream)
-                        else:
-                            N.call(f"cgp_axpby_{sfx}", 1.0, N.ptr(dst), c, N.ptr(bufs[b]),
-                                   N.ptr(dst), n * ne, stream)
+                    _axpby_terms(sfx, [(c, bufs[b]) for c, b in st.terms], bufs[st.dst],
+                                 n * cs.elems(st.dst), stream)
                 else:
-                    raise AssertionError(st.fn)
+                    if st.fn in ("conv", "conv_ntk"):
+                        what = "cgp_covntk_conv" if ntk else "cgp_cov_conv"
+                        r = N.CovConvNtkArgs() if ntk else N.CovConvArgs()
+                        stencil(pairwise(maps(r, st), st), st)
+                        r.post, r.flags = st.post, flags
+                    elif st.fn in ("nonlin", "nonlin_ntk"):
+                        what = "cgp_covntk_nonlin" if ntk else "cgp_cov_nonlin"
+                        r = N.CovNonlinNtkArgs() if ntk else N.CovNonlinArgs()
+                        pairwise(maps(r, st), st)
+                        r.kind, r.flags = st.post, flags
+                    elif st.fn == "gelu":
+                        what = "cgp_gelu_cov"
+                        r = pairwise(maps(N.GeluCovArgs(), st), st)
+                    elif st.fn == "avgpool":
+                        what = "cgp_covmap_avgpool"
+                        r = maps(N.CovAvgPoolArgs(), st)
+                        r.ho, r.wo, r.k, r.stride = h, w, st.op.geom.taps, st.op.geom.stride
+                    elif st.fn == "corrconv":
+                        what = "cgp_corrconv"
+                        r = stencil(maps(N.CorrConvArgs(), st), st)
+                        rr, rc = self._corr_tables(st.op, dev, x.dtype)
+                        r.corr_rows, r.corr_cols = N.ptr(rr), N.ptr(rc)
+                    else:
+                        raise AssertionError(st.fn)
+                    N.check(getattr(lib, f"{what}_{sfx}")(r, stream), what)
                 if st.dst in diag_out:
                     N.check(getattr(lib, f"cgp_covmap_diag_{sfx}")(
-                        N.ptr(dst), N.ptr(pi), n, h, w, N.ptr(diag_out[st.dst]), stream),
-                        "cgp_covmap_diag")
+                        dst, pi, n, h, w, N.ptr(diag_out[st.dst]), stream), "cgp_covmap_diag")
                 for b in st.free:
                     del bufs[b]
-        return out
+        out_k = outs.get(cs.final)
+        if last is None and cs.final_theta == cs.final:
+            return out_k, out_k.clone()
+        return out_k, outs.get(cs.final_theta)
