@@ -38,6 +38,14 @@ inline hipError_t stream_device(hipStream_t s, int* dev) {
 // ----------------------------------------------------------------------------------
 // n / d for 0 <= n < 2^31 by multiply-high ("division by invariant integers"):
 // q = (umulhi(n, m) + n) >> s with s = ceil(log2 d), m = floor(2^32 (2^s - d) / d) + 1.
+//
+// The add is a 32-bit one: umulhi(n, m) <= n, so it is exact for n < 2^31 and may wrap
+// beyond.  cov_moments_kernel, cov_nonlin_kernel (covpool.hip), gelu_cov_kernel (gelu.hip) and
+// cov_nonlin_ntk_kernel (covntk.hip) divide r0 + e by (h·w)², with r0 < (h·w)² a chunk's
+// offset in its first pair and e < 2048: they rely on their files' kMaxPairElems = 2^30 for
+// r0 + e <= 2^30 + 2046 < 2^31.  The conv, avgpool and corrconv kernels divide indices into
+// one workgroup's staged or written elements: at most 2^30, by the 64 KB of LDS it may take
+// and the same cap on one map.  cgp_selftest checks these divisors and numerators on the host.
 // ----------------------------------------------------------------------------------
 struct FastDiv {
     unsigned m, s, d;

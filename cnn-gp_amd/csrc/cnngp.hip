@@ -1781,13 +1781,18 @@ int cgp_var_chain_f64(const cgp_var_args* a, void* stream) { return var_chain_im
 int cgp_var_chain_f32(const cgp_var_args* a, void* stream) { return var_chain_impl<float>(a, stream); }
 
 int cgp_selftest(void) {
-    // FastDiv against exact division: every divisor the kernels use, edge numerators
+    // FastDiv against exact division: every divisor the kernels use, edge numerators.
+    // 38416, 614656, 1046529, 2^30 - 1 and 2^30 are the (h·w)² the position-pair kernels
+    // divide by (14x14, 28x28, 33x31 maps and the cap kMaxPairElems); d + 2046 is the largest
+    // r0 + e their elementwise kernels form (cgp_common.h, at fdiv), d + 2047 one past it
     const unsigned divs[] = {1, 2, 3, 5, 7, 8, 14, 28, 49, 196, 784, 1000, 1024, 4095, 4096,
-                             40000, 65535, 1000003u, 0x7fffffffu};
+                             38416, 40000, 65535, 614656, 1000003u, 1046529, (1u << 30) - 1,
+                             1u << 30, 0x7fffffffu};
     unsigned long long seed = 0x9e3779b97f4a7c15ull;
     for (unsigned d : divs) {
         const FastDiv f = make_fastdiv(d);
-        const unsigned edge[] = {0u, 1u, d - 1, d, d + 1, 2 * d - 1, 0x7ffffffeu, 0x7fffffffu};
+        const unsigned edge[] = {0u, 1u, d - 1, d, d + 1, 2 * d - 1, d + 2046, d + 2047,
+                                 0x7ffffffeu, 0x7fffffffu};
         for (unsigned n : edge)
             if (n < 0x80000000u && fdiv(n, f) != n / d)
                 return fail(CGP_EINVAL, "fastdiv %u / %u", n, d);

@@ -47,6 +47,8 @@ def corrconv_terms(s, k, stride, off, dil, ho, wo, rr, rc):
         for b in range(k):
             c1, k2 = idx(w, wo, b)
             for a2 in range(k):
+                if rr[a][a2] == 0.0:             # every weight below is zero (a band's rows)
+                    continue
                 r2, k3 = idx(h, ho, a2)
                 for b2 in range(k):
                     c2, k4 = idx(w, wo, b2)
