@@ -165,6 +165,24 @@ class CovConvNtkArgs(ctypes.Structure):
     ]
 
 
+class ABReluArgs(ctypes.Structure):
+    """Mirror of cgp_abrelu_args (include/cnngp.h): cgp_erf_args' fields, then s, m, h."""
+    _fields_ = list(ErfArgs._fields_) + [("s", _f64), ("m", _f64), ("h", _f64)]
+
+
+class ABReluCovArgs(ctypes.Structure):
+    """Mirror of cgp_abrelu_cov_args (include/cnngp.h): cgp_covntk_nonlin_args' maps, without
+    kind, then s, m, hh (h is the map's height)."""
+    _fields_ = [
+        ("in_", _vp), ("theta", _vp), ("out", _vp), ("out_theta", _vp),
+        ("addend", _vp), ("addend_theta", _vp), ("xx", _vp), ("yy", _vp),
+        ("pair_i", _vp), ("pair_j", _vp),
+        ("npairs", _i64),
+        ("h", _i32), ("w", _i32), ("same", _i32), ("flags", _i32),
+        ("s", _f64), ("m", _f64), ("hh", _f64),
+    ]
+
+
 class NetOp(ctypes.Structure):
     """Mirror of cgp_net_op (include/cnngp.h)."""
     _fields_ = [
@@ -281,6 +299,14 @@ SIGNATURES = {
     "cgp_covntk_conv_args_size": (ctypes.c_size_t, []),
     "cgp_covntk_conv_f64": (_i32, [ctypes.POINTER(CovConvNtkArgs), _vp]),
     "cgp_covntk_conv_f32": (_i32, [ctypes.POINTER(CovConvNtkArgs), _vp]),
+    "cgp_abrelu_args_size": (ctypes.c_size_t, []),
+    "cgp_abrelu_f64": (_i32, [ctypes.POINTER(ABReluArgs), _vp]),
+    "cgp_abrelu_f32": (_i32, [ctypes.POINTER(ABReluArgs), _vp]),
+    "cgp_var_abrelu_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _f64, _vp, _vp, _vp]),
+    "cgp_var_abrelu_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _f64, _vp, _vp, _vp]),
+    "cgp_abrelu_cov_args_size": (ctypes.c_size_t, []),
+    "cgp_abrelu_cov_f64": (_i32, [ctypes.POINTER(ABReluCovArgs), _vp]),
+    "cgp_abrelu_cov_f32": (_i32, [ctypes.POINTER(ABReluCovArgs), _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_axpby_f32": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_scale_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _f64, _vp]),
@@ -358,6 +384,8 @@ def load():
                 lib.cgp_corrconv_args_size() != ctypes.sizeof(CorrConvArgs) or \
                 lib.cgp_gelu_args_size() != ctypes.sizeof(GeluArgs) or \
                 lib.cgp_gelu_cov_args_size() != ctypes.sizeof(GeluCovArgs) or \
+                lib.cgp_abrelu_args_size() != ctypes.sizeof(ABReluArgs) or \
+                lib.cgp_abrelu_cov_args_size() != ctypes.sizeof(ABReluCovArgs) or \
                 lib.cgp_covntk_nonlin_args_size() != ctypes.sizeof(CovNonlinNtkArgs) or \
                 lib.cgp_covntk_conv_args_size() != ctypes.sizeof(CovConvNtkArgs) or \
                 lib.cgp_net_op_size() != ctypes.sizeof(NetOp) or \

@@ -8,6 +8,7 @@ storage only: no torch compute runs on the pair maps.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Optional
 
@@ -25,7 +26,8 @@ VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
 # behind the default; set_ntk_maps_fusion overrides it per model)
 NTK_MAPS_FUSED = True
 
-__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "Gelu", "GlobalAvgPool", "AvgPool2d",
+__all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "Gelu", "ABReLU", "LeakyReLU",
+           "GlobalAvgPool", "AvgPool2d",
            "CorrelatedConv2d", "rbf_corr", "band_corr", "Sequential", "Mixture", "Sum",
            "resnet_block")
 
@@ -171,6 +173,9 @@ class NNGPKernel(nn.Module):
                 key.append(("r", d["kernel_size"], d["stride"], d["_padding_arg"], d["padding"],
                             d["dilation"], float(d["var_weight"]), float(d["var_bias"]),
                             d["lengthscale"], d["corr_rows"], d["corr_cols"]))
+            elif isinstance(m, ABReLU):
+                # the slopes are in the op records: a plan serves one (a, b)
+                key.append(("ab", float(d["a"]), float(d["b"])))
             elif isinstance(m, Mixture):
                 mixture = True
                 key.append(("m", tuple(m.proportions())))
@@ -226,7 +231,8 @@ class NNGPKernel(nn.Module):
         """Evaluate the ReLU map op by op exactly like the reference (correctly rounded
         1/sqrt, sqrt, acos, division) instead of the closed form (default; within 1e-14 of
         the exact map, see csrc/relu_poly.h).  For parity studies; ~2x slower.  An Erf and
-        a Gelu have one evaluation mode and ignore it."""
+        a Gelu have one evaluation mode and ignore it; an ABReLU / LeakyReLU evaluates the
+        ReLU map inside it in the chosen mode."""
         for m in self.modules():
             m.__dict__["_cgp_exact_relu"] = bool(enabled)
         return self
@@ -312,6 +318,9 @@ class NNGPKernel(nn.Module):
                             (1/Δ² + (1 − v₁v₂)/((1 + v₁)(1 + v₂)) + 1)·t/2π + 1/4 + atan(t)/2π,
                             t = c/Δ, Δ² = (1 + v₁)(1 + v₂) − c² raised to 1 below 1; the same
                             at c = v₁ = v₂ = v where K' is overridden  
+            ABReLU(a, b)    K' as forward,         Θ' = Θ·κ̇,  κ̇ = (a − b)²·(π - θ)/2π + ab
+                            with the ReLU's θ; Θ' = Θ·(a² + b²)/2 where K' is overridden
+                            
             Sum / Mixture   the same (weighted) sum on both
 
         and the result is Θ of the final 1x1 value; a model without a Conv2d gives zeros
@@ -503,14 +512,14 @@ class NNGPKernel(nn.Module):
         """The neural tangent kernel Θ, [N1, N2] (or [N1] when diag), carried on position-pair
         maps; with ``return_nngp`` the pair (K, Θ).  Valid for every model forward runs on
         position-pair maps -- a GlobalAvgPool, AvgPool2d or CorrelatedConv2d anywhere the
-        forward rules allow, with ReLU, Erf and Gelu -- and for a model with none of them,
+        forward rules allow, with ReLU, Erf, Gelu and ABReLU -- and for a model with none of them,
         where it is a second, slower route to ``ntk``'s result.
 
         The recursion is ntk's, with the pooling layers the same linear op on both streams
         and a CorrelatedConv2d the conv's rule with its own stencil:
 
             Conv2d, CorrelatedConv2d   K' = A(K) + var_bias,  Θ' = A(Θ) + K'
-            ReLU / Erf / Gelu          K' as forward,         Θ' = Θ·κ̇   (ntk's κ̇ of
+            ReLU / Erf / Gelu / ABReLU K' as forward,         Θ' = Θ·κ̇   (ntk's κ̇ of
                                        (S[p, q], xx_i[p], yy_j[q]); the override's value
                                        where same, i = j and p = q)
             AvgPool2d, GlobalAvgPool   the same average of K and of Θ
@@ -743,6 +752,61 @@ class Gelu(NNGPKernel):
 
     def layers(self):
         return 0
+
+
+class ABReLU(NNGPKernel):
+    """The two-slope ReLU φ(x) = a·min(x, 0) + b·max(x, 0) (no reference counterpart):
+    LeakyReLU is (slope, 1), |x| is (−1, 1), a damped identity is (a, a), ReLU is (0, 1).  With
+    R the ReLU map and k its κ̇, K' = (a − b)²·R + ab·c, κ̇ = (a − b)²·k + ab, and
+    (a² + b²)/2 times the variance where the ReLU overrides (device: abrelu_elem).
+    Usable wherever Gelu is: forward, ntk, position_covariance, the pooled path and ntk_maps;
+    a model with one runs on the layer path, and set_exact_relu applies to it as to ReLU.
+    The slopes are plain floats: assigning ``a`` or ``b`` takes effect at the next call.  The
+    map is homogeneous of degree 1 and K' can be negative."""
+
+    def __init__(self, a, b):
+        super().__init__()
+        self.a = float(a)
+        self.b = float(b)
+        self._check()
+
+    def _check(self):
+        a, b = float(self.a), float(self.b)
+        if not (math.isfinite(a) and math.isfinite(b)):
+            raise ValueError(f"{type(self).__name__}: the slopes must be finite, got ({a}, {b})")
+        if a == 0.0 and b == 0.0:
+            raise ValueError(f"{type(self).__name__}: both slopes are zero (φ = 0)")
+        return a, b
+
+    def constants(self):
+        """(s, m, h) = ((a − b)², a·b, (a² + b²)/2) in double: what the kernels take."""
+        a, b = self._check()
+        return (a - b) * (a - b), a * b, (a * a + b * b) / 2
+
+    def layers(self):
+        return 0
+
+    def extra_repr(self):
+        return f"a={self.a}, b={self.b}"
+
+
+class LeakyReLU(ABReLU):
+    """φ(x) = max(x, 0) + negative_slope·min(x, 0): ABReLU(negative_slope, 1), with torch's
+    default slope."""
+
+    def __init__(self, negative_slope=0.01):
+        super().__init__(negative_slope, 1.0)
+
+    @property
+    def negative_slope(self):
+        return self.a
+
+    @negative_slope.setter
+    def negative_slope(self, value):
+        self.a = float(value)
+
+    def extra_repr(self):
+        return f"negative_slope={self.a}"
 
 
 class GlobalAvgPool(NNGPKernel):

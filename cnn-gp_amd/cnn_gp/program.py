@@ -9,6 +9,7 @@ whole [N1·N2, 1, H, W] covariance tensor.  Here the tree is flattened once into
     v  = relu(u)                     kernels.py:134-165
     v  = erf(u)                      Erf (no reference counterpart)
     v  = gelu(u)                     Gelu (no reference counterpart)
+    v  = abrelu(u; a, b)             ABReLU / LeakyReLU (no reference counterpart)
     v  = add[(coef, u), ...]         Sum (kernels.py:252-254) / Mixture (:220-225)
     v  = pool(u)                     GlobalAvgPool (no reference counterpart; DESIGN §3.3:
                                      such a program runs on position-pair maps, pool_steps)
@@ -21,13 +22,12 @@ and then split into two device pipelines:
 
 * the VARIANCE pipeline runs every op, unfused, on the per-image maps [xx | yy]
   ((N1 + N2) maps — negligible next to the N1·N2 pair maps) and keeps the variances
-  of every value a ReLU, Erf or Gelu consumes;
+  of every value a ReLU, Erf, Gelu or ABReLU consumes;
 * the PAIR pipeline runs on the N1·N2 maps with ops fused so each HBM pass does the
   most work:  [ReLU|moments] → Conv → [ReLU] → [+ addend]  is ONE kernel
   (cgp_conv_*), a ReLU not adjacent to a single-use conv is cgp_relu_* (+ addend),
-  an Erf or a Gelu is always its own pass cgp_erf_* / cgp_gelu_* (+ addend), and only sums
-  that cannot be
-  folded into their producer run as cgp_axpby_*.
+  an Erf, a Gelu or an ABReLU is always its own pass cgp_erf_* / cgp_gelu_* / cgp_abrelu_*
+  (+ addend), and only sums that cannot be folded into their producer run as cgp_axpby_*.
 
 Fusion changes no arithmetic: each fused stage performs exactly the operations of the
 op it replaces (a + b == b + a in IEEE, so folding a Sum into either branch is exact).
@@ -73,7 +73,8 @@ class CorrGeom(ConvGeom):
 
 @dataclasses.dataclass
 class Op:
-    # 'conv' | 'relu' | 'erf' | 'gelu' | 'add' | 'pool' | 'avgpool' | 'corrconv' | 'moments'
+    # 'conv' | 'relu' | 'erf' | 'gelu' | 'abrelu' | 'add' | 'pool' | 'avgpool' | 'corrconv' |
+    # 'moments'
     kind: str
     dst: int
     src: Optional[int] = None
@@ -87,6 +88,10 @@ class Op:
     post: int = N.CGP_POST_NONE
     post_var: Optional[int] = None
     addend: Optional[int] = None
+    # abrelu: the slopes (a, b) and the kernels' constants (s, m, h) =
+    # ((a − b)², a·b, (a² + b²)/2), computed in double
+    slopes: Optional[tuple] = None
+    smh: Optional[tuple] = None
 
 
 class Program:
@@ -196,6 +201,12 @@ def _emit(prog: Program, mod, v: int) -> int:
         prog.ops.append(Op("gelu", out, src=v, shape_in=prog.shapes[v],
                            shape_out=prog.shapes[v]))
         return out
+    if isinstance(mod, K.ABReLU):
+        out = prog.new_value(prog.shapes[v])
+        prog.ops.append(Op("abrelu", out, src=v, shape_in=prog.shapes[v],
+                           shape_out=prog.shapes[v], slopes=(float(mod.a), float(mod.b)),
+                           smh=mod.constants()))
+        return out
     if isinstance(mod, K.GlobalAvgPool):
         out = prog.new_value((1, 1))
         prog.ops.append(Op("pool", out, src=v, shape_in=prog.shapes[v], shape_out=(1, 1)))
@@ -260,9 +271,9 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
          fold_moments: bool = True) -> list:
     """Return the fused op list for the pair pipeline (prog.ops is left untouched).
     ``pre_relu`` / ``fold_moments`` enable rules 3 / 4 (the whole-network kernel keeps
-    standalone ReLU and moments ops: in LDS they cost no extra memory pass).  An erf or gelu
-    op is never a conv's pre- or post-stage (rules 1 and 3 match ReLU only); rule 2 may give
-    it an addend."""
+    standalone ReLU and moments ops: in LDS they cost no extra memory pass).  An erf, gelu or
+    abrelu op is never a conv's pre- or post-stage (rules 1 and 3 match ReLU only); rule 2 may
+    give it an addend."""
     ops = [dataclasses.replace(o, terms=list(o.terms)) for o in prog.ops]
     if not enable:
         return ops
@@ -298,7 +309,7 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
             (_, t0), (_, t1) = a.terms
             for cand, other in ((t1, t0), (t0, t1)):
                 pi = producer(ops, cand)
-                if pi is None or ops[pi].kind not in ("conv", "relu", "erf", "gelu") or \
+                if pi is None or ops[pi].kind not in ("conv", "relu", "erf", "gelu", "abrelu") or \
                         ops[pi].addend is not None or uses.get(cand, 0) != 1:
                     continue
                 oi = producer(ops, other)
@@ -344,10 +355,14 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
     return ops
 
 
+# the op kinds that read the per-image variances of their source
+NONLIN_KINDS = ("relu", "erf", "gelu", "abrelu")
+
+
 def needed_variances(ops) -> set:
     need = set()
     for o in ops:
-        if o.kind in ("relu", "erf", "gelu"):
+        if o.kind in NONLIN_KINDS:
             need.add(o.src)
         if o.pre == N.CGP_PRE_RELU:
             need.add(o.pre_var)
@@ -372,6 +387,8 @@ class NtkStep:
     fn "erf_ntk":  dst, dst_theta = erf(src), theta·κ̇                    cgp_erf_*
     fn "gelu":     dst = gelu(src), variances of value ``var``           cgp_gelu_* (theta NULL)
     fn "gelu_ntk": dst, dst_theta = gelu(src), theta·κ̇                   cgp_gelu_*
+    fn "abrelu":   dst = abrelu(src; op.smh), variances of ``var``       cgp_abrelu_* (theta NULL)
+    fn "abrelu_ntk": dst, dst_theta = abrelu(src), theta·κ̇               cgp_abrelu_*
     fn "axpby":    dst = Σ coef·buffer over ``terms`` (coef None: 1)     cgp_axpby_*
     """
     fn: str
@@ -406,11 +423,12 @@ def ntk_steps(prog: Program, v0: int, vf: int):
                         reference overrides K': same and i = j, or same and diag)
         Erf             K' = erf(K),           Θ' = Θ·κ̇,  κ̇ = (4/π)/√D  
         Gelu            K' = gelu(K),          Θ' = Θ·κ̇,  κ̇ = E[φ'φ']   
+        ABReLU          K' = abrelu(K),        Θ' = Θ·κ̇,  κ̇ = s·(π - θ)/2π + m  
         Sum / Mixture   the same (weighted) sum on both streams
 
     A zero Θ is carried as None and costs nothing: the first conv's Θ' IS its K' (the same
-    buffer), a ReLU / Erf / Gelu on a value with Θ = 0 is the plain cgp_relu_* / forward-only
-    cgp_erf_* / cgp_gelu_*, sums skip zero terms
+    buffer), a ReLU / Erf / Gelu / ABReLU on a value with Θ = 0 is the plain cgp_relu_* /
+    forward-only cgp_erf_* / cgp_gelu_* / cgp_abrelu_*, sums skip zero terms
     (a sum whose only non-zero term has weight 1 passes that term's buffer on)."""
     steps = []
     theta = {v0: None}
@@ -424,7 +442,7 @@ def ntk_steps(prog: Program, v0: int, vf: int):
                 steps.append(NtkStep("conv", ("T", d), src=theta[op.src], op=op, bias=0.0,
                                      addend=("K", d)))
                 theta[d] = ("T", d)
-        elif op.kind in ("relu", "erf", "gelu"):
+        elif op.kind in NONLIN_KINDS:
             if theta[op.src] is None:
                 steps.append(NtkStep(op.kind, ("K", d), src=("K", op.src), op=op, var=op.src))
                 theta[d] = None
@@ -467,6 +485,8 @@ CORRCONV_RULE_GLOBAL = ("a CorrelatedConv2d downstream of a GlobalAvgPool is not
                         "the value there is 1x1 per pair, with no taps to correlate (DESIGN §8)")
 GELU_RULE_GLOBAL = ("a Gelu downstream of a GlobalAvgPool is not implemented: it would need "
                     "the pooled self-covariances of each image (DESIGN §8)")
+ABRELU_RULE_GLOBAL = ("an ABReLU / LeakyReLU downstream of a GlobalAvgPool is not implemented: "
+                      "it would need the pooled self-covariances of each image (DESIGN §8)")
 CORRCONV_RULE_NTK = ("ntk: the neural tangent kernel of a model with a CorrelatedConv2d is not "
                      "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
 
@@ -486,6 +506,8 @@ class CovStep:
                   [+ addend]                                             cgp_cov_nonlin_*
     fn "gelu":    dst = gelu of src, variances of value ``var`` [+ addend]
                                                                          cgp_gelu_cov_*
+    fn "abrelu":  dst = abrelu of src (op.smh), variances of value ``var`` [+ addend]
+                                                                         cgp_abrelu_cov_*
     fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
     fn "avgpool": dst = mean of src over the windows of p and of q (op.geom)
                                                                          cgp_covmap_avgpool_*
@@ -499,6 +521,8 @@ class CovStep:
                                                                           cgp_covntk_conv_*
     fn "nonlin_ntk": dst, dst_theta = ``post`` of src [+ addend], theta·κ̇ [+ addend_theta]
                                                                           cgp_covntk_nonlin_*
+    fn "abrelu_ntk": dst, dst_theta = abrelu of src [+ addend], theta·κ̇ [+ addend_theta]
+                                                                          cgp_abrelu_cov_*
     fn "accum":      dst = dst + src, in place                            cgp_axpby_*
     ``free``: the buffers nothing reads after this launch."""
     fn: str
@@ -580,7 +604,7 @@ def _schedule(cs: CovSteps, keep, key=None):
 
 # op kind -> the rule it breaks downstream of a GlobalAvgPool (its result is not pooled)
 POOL_RULES = {"relu": POOL_RULE_NONLIN, "erf": POOL_RULE_NONLIN, "gelu": GELU_RULE_GLOBAL,
-              "avgpool": AVGPOOL_RULE_GLOBAL, "corrconv": CORRCONV_RULE_GLOBAL}
+              "abrelu": ABRELU_RULE_GLOBAL, "avgpool": AVGPOOL_RULE_GLOBAL, "corrconv": CORRCONV_RULE_GLOBAL}
 
 
 def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
@@ -596,8 +620,8 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
     variances are the diagonal of the conv's output on the self pairs, which has to exist
     as a map to be read.
 
-    Raises NotImplementedError naming the rule for a ReLU / Erf, a Gelu, an AvgPool2d or a
-    CorrelatedConv2d after a GlobalAvgPool and for a path that does not pass exactly one
+    Raises NotImplementedError naming the rule for a ReLU / Erf, a Gelu, an ABReLU, an AvgPool2d
+    or a CorrelatedConv2d after a GlobalAvgPool and for a path that does not pass exactly one
     GlobalAvgPool."""
     pooled = {v0: False}
     avgpooled = {v0: False}
@@ -647,8 +671,8 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
             steps.append(CovStep("nonlin", op.dst, src=op.src, op=op,
                                  post=N.CGP_COV_RELU if op.kind == "relu" else N.CGP_COV_ERF,
                                  var=op.src, addend=op.addend))
-        elif op.kind == "gelu":
-            steps.append(CovStep("gelu", op.dst, src=op.src, op=op, var=op.src,
+        elif op.kind in ("gelu", "abrelu"):
+            steps.append(CovStep(op.kind, op.dst, src=op.src, op=op, var=op.src,
                                  addend=op.addend))
         elif op.kind in ("pool", "avgpool"):
             steps.append(CovStep(op.kind, op.dst, src=op.src, op=op))
@@ -694,6 +718,8 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
         Conv2d, CorrelatedConv2d   K' = A(K) + b,   Θ' = A(Θ) + K'   (correlated weights are a
                                    fixed linear map of i.i.d. parameters: the conv's rule, A_R)
         ReLU / Erf / Gelu          K' as forward,   Θ' = Θ·κ̇
+        ABReLU                     K' as forward,   Θ' = Θ·κ̇   (cgp_abrelu_cov_* with theta: a
+                                   launch of its own, never a conv's post-stage)
         AvgPool2d, GlobalAvgPool   the same linear op on both
         Sum / Mixture              the same (weighted) sum on both
 
@@ -776,6 +802,16 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
                              post=N.CGP_COV_GELU if st.fn == "gelu" else st.post,
                              var=st.var, addend=ka, theta=ts, dst_theta=("T", d),
                              addend_theta=ta), shape, sc)
+                theta[d] = ("T", d)
+        elif st.fn == "abrelu":
+            # a launch of its own on either run: one entry point, with and without Θ
+            if ts is None:
+                emit(CovStep("abrelu", K(d), src=K(st.src), op=op, var=st.var, addend=ka),
+                     shape, sc)
+                theta[d] = ta
+            else:
+                emit(CovStep("abrelu_ntk", K(d), src=K(st.src), op=op, var=st.var, addend=ka,
+                             theta=ts, dst_theta=("T", d), addend_theta=ta), shape, sc)
                 theta[d] = ("T", d)
         elif st.fn in ("pool", "avgpool"):
             emit(CovStep(st.fn, K(d), src=K(st.src), op=op), shape, sc)
@@ -872,6 +908,18 @@ class Plan:
             return "f32"
         raise TypeError(f"unsupported dtype {dtype} (float32 or float64)")
 
+    def _nonlin_args(self, op):
+        """The argument record of an erf / gelu / abrelu op's layer-path entry point, with
+        what the op itself fixes: an abrelu's constants and the ReLU evaluation mode."""
+        if op.kind == "erf":
+            return N.ErfArgs()
+        if op.kind == "gelu":
+            return N.GeluArgs()
+        r = N.ABReluArgs()
+        r.s, r.m, r.h = op.smh
+        r.flags = self.flags
+        return r
+
     def _last_use(self, ops, extra_final):
         last = {}
         for idx, o in enumerate(ops):
@@ -885,7 +933,8 @@ class Plan:
 
     # -- variance pipeline --------------------------------------------------------------
     def run_variances(self, xx0, yy0, n1, n2, same, stream, need=None):
-        """Per-image variance maps of every value a ReLU, Erf or Gelu reads (or of ``need``).
+        """Per-image variance maps of every value a ReLU, Erf, Gelu or ABReLU reads (or of
+        ``need``).
         xx0/yy0: [n, H, W]."""
         sfx = self._sfx(xx0.dtype)
         dev = xx0.device
@@ -929,6 +978,12 @@ class Plan:
                 N.call(f"cgp_var_{op.kind}_{sfx}", N.ptr(xin), N.ptr(yin), n1, n2, ho * wo,
                        int(same), N.ptr(buf[:n1]), N.ptr(buf[n1:]), stream)
                 out = (buf[:n1], buf[n1:])
+            elif op.kind == "abrelu":
+                xin, yin = vals[op.src]
+                buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
+                N.call(f"cgp_var_abrelu_{sfx}", N.ptr(xin), N.ptr(yin), n1, n2, ho * wo,
+                       int(same), op.smh[2], N.ptr(buf[:n1]), N.ptr(buf[n1:]), stream)
+                out = (buf[:n1], buf[n1:])
             elif op.kind == "add":
                 buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
                 outx, outy = buf[:n1], buf[n1:]
@@ -953,7 +1008,7 @@ class Plan:
         """cgp_var_op records of the variance program (cached per need/quarter/device):
         LDS slots by first fit over the values' live ranges, store offsets per image.
         None when the program has an op the chain kernel lacks (a Sum of > 4 terms, an
-        Erf, a Gelu).  The records are uploaded once per plan, need set and device, and the
+        Erf, a Gelu, an ABReLU).  The records are uploaded once per plan, need set and device, and the
         copy is synchronous (on the uploading stream alone, not the device): the records are
         shared by every stream that runs the plan, and none may see a copy in flight."""
         key = (frozenset(need), frozenset(quarter), str(dev))
@@ -1153,10 +1208,10 @@ class Plan:
                 r.flags = self.flags
                 fn = getattr(lib, f"cgp_relu_{sfx}")
                 launch = (lambda fn=fn, r=r: N.check(fn(r, stream), "cgp_relu"))
-            elif op.kind in ("erf", "gelu"):
+            elif op.kind in ("erf", "gelu", "abrelu"):
                 out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
                 vx, vy = var[op.src]
-                r = N.ErfArgs() if op.kind == "erf" else N.GeluArgs()
+                r = self._nonlin_args(op)
                 r.xy, r.out_xy = N.ptr(vals[op.src]), N.ptr(out)
                 r.addend = N.ptr(vals[op.addend]) if op.addend is not None else None
                 r.xx, r.yy = N.ptr(vx), N.ptr(vy)
@@ -1184,9 +1239,9 @@ class Plan:
 
     # -- NTK: K and Θ through the unfused program ------------------------------------------
     def ntk_need_var(self) -> set:
-        """The values whose variance maps the NTK run reads: every ReLU's, Erf's and Gelu's
-        source in the unfused program (run_variances(need=...))."""
-        return {o.src for o in self.prog.ops if o.kind in ("relu", "erf", "gelu")}
+        """The values whose variance maps the NTK run reads: every ReLU's, Erf's, Gelu's and
+        ABReLU's source in the unfused program (run_variances(need=...))."""
+        return {o.src for o in self.prog.ops if o.kind in NONLIN_KINDS}
 
     def run_pairs_ntk(self, xy0, var, n1, n2, same, diag, stream):
         """Runs ntk_steps on the pair maps; returns (K, Θ) of the final value as
@@ -1257,10 +1312,10 @@ class Plan:
                 r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
                 r.flags = self.flags
                 N.check(getattr(lib, f"cgp_relu_ntk_{sfx}")(r, stream), "cgp_relu_ntk")
-            elif st.fn in ("erf", "erf_ntk", "gelu", "gelu_ntk"):
+            elif st.fn in ("erf", "erf_ntk", "gelu", "gelu_ntk", "abrelu", "abrelu_ntk"):
                 out = bufs[st.dst] = new(op)
                 vx, vy = var[st.var]
-                r = N.ErfArgs() if op.kind == "erf" else N.GeluArgs()
+                r = self._nonlin_args(op)
                 r.xy, r.out_xy = N.ptr(bufs[st.src]), N.ptr(out)
                 if st.fn.endswith("_ntk"):
                     tout = bufs[st.dst_theta] = new(op)
@@ -1449,6 +1504,11 @@ class Plan:
                     elif st.fn == "gelu":
                         what = "cgp_gelu_cov"
                         r = pairwise(maps(N.GeluCovArgs(), st), st)
+                    elif st.fn in ("abrelu", "abrelu_ntk"):
+                        what = "cgp_abrelu_cov"
+                        r = pairwise(maps(N.ABReluCovArgs(), st), st)
+                        r.s, r.m, r.hh = st.op.smh
+                        r.flags = flags
                     elif st.fn == "avgpool":
                         what = "cgp_covmap_avgpool"
                         r = maps(N.CovAvgPoolArgs(), st)

@@ -577,6 +577,85 @@ int cgp_covntk_conv_f64(const cgp_covntk_conv_args* args, void* stream);
 int cgp_covntk_conv_f32(const cgp_covntk_conv_args* args, void* stream);
 
 /*
+ * The two-slope ReLU φ(x) = a·min(x, 0) + b·max(x, 0) (additions to ABI 12: no struct or
+ * existing entry point changed; no reference counterpart): the leaky ReLU
+ * (a = slope, b = 1), |x| (a = -1, b = 1), a damped identity (a = b), the ReLU itself (a = 0,
+ * b = 1).  In the conventions of the ReLU entry points above -- per pixel (xy, xx, yy) =
+ * (c, v1, v2), no rescaling.  With R(c, v1, v2) the map of cgp_relu_* (closed form, or op by
+ * op with CGP_FLAG_EXACT_RELU) and k(c, v1, v2) = (π - θ)/2π the κ̇ of cgp_relu_ntk_*, the
+ * same device functions, and three constants the caller computes in double,
+ *   s = (a - b)²,  m = a·b,  h = (a² + b²)/2     (each rounded once to the map's type),
+ *   pair map    out_xy = fma(s, R, m·c)          (the product rounded, then one fma)
+ *   variances   v' = h·v
+ *   NTK         out_theta = theta·κ̇,  κ̇ = fma(s, k, m) = E[φ'(u1)·φ'(u2)]
+ * from φ(x) = b·relu(x) - a·relu(-x) and R(θ) - R(π - θ) = c/2.  Where cgp_relu_* overrides
+ * its map (same && !diag: pairs i == j; same && diag: all), out_xy = h·v1, the bits
+ * cgp_var_abrelu_* writes, and out_theta = theta·h.  So for finite inputs (s, m, h) =
+ * (1, 0, 1/2) gives the bits of cgp_relu_* / cgp_relu_ntk_* / cgp_var_relu_*, and (0, 1, 1)
+ * returns xy, theta and the variances unchanged.  The map is homogeneous of degree 1;
+ * out_xy can be negative (c < 0, or a·b < 0).  A non-finite s, m or h is CGP_EINVAL.
+ *
+ * cgp_abrelu_args has the fields and the rules of cgp_erf_args, then s, m, h: theta == NULL
+ * is the forward-only pass; in-place (out_xy == xy, out_theta == theta) is allowed, and theta
+ * may be xy itself; addend (optional) is added to out_xy only, as a separate rounding; same
+ * or diag need n1 == n2; hw is at most 2048; nmaps < 2^31.
+ */
+typedef struct cgp_abrelu_args {
+    const void* xy;         /* [nmaps][hw] */
+    const void* theta;      /* [nmaps][hw] or NULL */
+    void* out_xy;           /* [nmaps][hw] */
+    void* out_theta;        /* [nmaps][hw] (unused when theta is NULL) */
+    const void* addend;     /* [nmaps][hw] or NULL */
+    const void* xx;         /* [n1][hw] variances at the nonlinearity's input */
+    const void* yy;         /* [n2][hw] (may be NULL when same && diag) */
+    int64_t nmaps, n1, n2;
+    int32_t hw, same, diag;
+    int32_t flags;          /* CGP_FLAG_EXACT_RELU */
+    double s, m, h;         /* (a - b)², a·b, (a² + b²)/2 */
+} cgp_abrelu_args;
+size_t cgp_abrelu_args_size(void);
+int cgp_abrelu_f64(const cgp_abrelu_args* args, void* stream);
+int cgp_abrelu_f32(const cgp_abrelu_args* args, void* stream);
+/* The two-slope ReLU on the per-image variances: xx' = h·xx; yy' = xx' if same else h·yy.
+ * xx: [n1][hw], yy: [n2][hw]. */
+int cgp_var_abrelu_f64(const double* xx, const double* yy, int64_t n1, int64_t n2, int32_t hw,
+                       int32_t same, double h, double* xx_out, double* yy_out, void* stream);
+int cgp_var_abrelu_f32(const float* xx, const float* yy, int64_t n1, int64_t n2, int32_t hw,
+                       int32_t same, double h, float* xx_out, float* yy_out, void* stream);
+/*
+ * The two-slope ReLU on position-pair maps, one entry point for both runs:
+ *   out       = map(in) [+ addend]               theta == NULL: this alone
+ *   out_theta = theta·κ̇ [+ addend_theta]         each a separate rounding
+ * with cgp_cov_nonlin_*'s element rule: (c, v1, v2) = (in[m][p, q], xx[pair_i[m]][p],
+ * yy[pair_j[m]][q]), and the override (out = h·xx[pair_i[m]][p], κ̇ = h) where same,
+ * pair_i[m] == pair_j[m] and p == q.  At (s, m, h) = (1, 0, 1/2) the outputs are the bits of
+ * cgp_cov_nonlin_* / cgp_covntk_nonlin_* with kind CGP_COV_RELU.  theta may be in, and
+ * in-place (out == in, out_theta == theta) is allowed: every element is read before it is
+ * written, by one thread.  out and out_theta are two buffers.  addend_theta is read only
+ * with theta.
+ */
+typedef struct cgp_abrelu_cov_args {
+    const void* in;            /* [npairs][h][h][w][w] */
+    const void* theta;         /* like in, or NULL: the forward-only pass */
+    void* out;
+    void* out_theta;           /* (unused when theta is NULL) */
+    const void* addend;        /* like out, or NULL */
+    const void* addend_theta;  /* like out_theta, or NULL */
+    const void* xx;            /* [n1][h][w] variances at the nonlinearity's input */
+    const void* yy;            /* [n2][h][w] (same: may be xx) */
+    const int32_t* pair_i;     /* device [npairs] */
+    const int32_t* pair_j;
+    int64_t npairs;
+    int32_t h, w;
+    int32_t same;
+    int32_t flags;             /* CGP_FLAG_EXACT_RELU */
+    double s, m, hh;           /* (a - b)², a·b, (a² + b²)/2 (hh: h is the map's height) */
+} cgp_abrelu_cov_args;
+size_t cgp_abrelu_cov_args_size(void);
+int cgp_abrelu_cov_f64(const cgp_abrelu_cov_args* args, void* stream);
+int cgp_abrelu_cov_f32(const cgp_abrelu_cov_args* args, void* stream);
+
+/*
  * out = alpha·a + beta·b (b may be NULL: out = alpha·a), n elements.  The unfused form
  * of Sum (alpha = beta = 1, kernel_patch.py:43-63) and Mixture (kernels.py:220-225).
  * Products and the sum are rounded separately (no FMA contraction), like torch.
