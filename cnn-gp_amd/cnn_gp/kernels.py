@@ -734,7 +734,7 @@ class ReLU(NNGPKernel):
 class Erf(NNGPKernel):
     """The erf nonlinearity (no reference counterpart; the paper's second closed form,
     Williams 1997): K' = (2/π)·asin(2c/√((1+2v₁)(1+2v₂))), evaluated in the atan form of
-    DESIGN §3.2 (device: erf_pair).  Runs on the layer path; set_exact_relu has no effect
+    DESIGN §3.2 (device: ErfMap).  Runs on the layer path; set_exact_relu has no effect
     on it."""
 
     def layers(self):
@@ -758,7 +758,7 @@ class ABReLU(NNGPKernel):
     """The two-slope ReLU φ(x) = a·min(x, 0) + b·max(x, 0) (no reference counterpart):
     LeakyReLU is (slope, 1), |x| is (−1, 1), a damped identity is (a, a), ReLU is (0, 1).  With
     R the ReLU map and k its κ̇, K' = (a − b)²·R + ab·c, κ̇ = (a − b)²·k + ab, and
-    (a² + b²)/2 times the variance where the ReLU overrides (device: abrelu_elem).
+    (a² + b²)/2 times the variance where the ReLU overrides (device: ABReluMap).
     Usable wherever Gelu is: forward, ntk, position_covariance, the pooled path and ntk_maps;
     a model with one runs on the layer path, and set_exact_relu applies to it as to ReLU.
     The slopes are plain floats: assigning ``a`` or ``b`` takes effect at the next call.  The

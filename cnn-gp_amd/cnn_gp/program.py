@@ -358,6 +358,18 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
 # the op kinds that read the per-image variances of their source
 NONLIN_KINDS = ("relu", "erf", "gelu", "abrelu")
 
+# The layer-path entry point cgp_<name>_* of every nonlinearity: its argument class, that
+# class's K' output field, whether the record takes the ReLU evaluation flags and the op's
+# (s, m, h), and what cgp_var_<kind>_* takes between `same` and its outputs.  The ReLU alone
+# has an entry point of its own for the two-stream form; the others take theta or NULL.
+NONLIN_CALLS = {
+    "relu": (N.ReluArgs, "out", True, False, lambda op: ()),
+    "relu_ntk": (N.ReluNtkArgs, "out_xy", True, False, None),
+    "erf": (N.ErfArgs, "out_xy", False, False, lambda op: ()),
+    "gelu": (N.GeluArgs, "out_xy", False, False, lambda op: ()),
+    "abrelu": (N.ABReluArgs, "out_xy", True, True, lambda op: (op.smh[2],)),
+}
+
 
 def needed_variances(ops) -> set:
     need = set()
@@ -908,17 +920,30 @@ class Plan:
             return "f32"
         raise TypeError(f"unsupported dtype {dtype} (float32 or float64)")
 
-    def _nonlin_args(self, op):
-        """The argument record of an erf / gelu / abrelu op's layer-path entry point, with
-        what the op itself fixes: an abrelu's constants and the ReLU evaluation mode."""
-        if op.kind == "erf":
-            return N.ErfArgs()
-        if op.kind == "gelu":
-            return N.GeluArgs()
-        r = N.ABReluArgs()
-        r.s, r.m, r.h = op.smh
-        r.flags = self.flags
-        return r
+    def _nonlin_launch(self, op, sfx, stream, src, out, var, n1, n2, same, diag, addend=None,
+                       theta=None, out_theta=None):
+        """Fills the argument record of a layer-path nonlinearity (NONLIN_CALLS) and returns the
+        closure that launches it; with ``theta`` the two-stream form (Θ' = Θ·κ̇)."""
+        name = "relu_ntk" if op.kind == "relu" and theta is not None else op.kind
+        cls, out_field, has_flags, has_smh = NONLIN_CALLS[name][:4]
+        vx, vy = var
+        ho, wo = op.shape_out
+        r = cls()
+        r.xy = N.ptr(src)
+        setattr(r, out_field, N.ptr(out))
+        if addend is not None:
+            r.addend = N.ptr(addend)
+        if theta is not None:
+            r.theta, r.out_theta = N.ptr(theta), N.ptr(out_theta)
+        r.xx, r.yy = N.ptr(vx), N.ptr(vy)
+        r.nmaps, r.n1, r.n2 = (n1 if diag else n1 * n2), n1, n2
+        r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
+        if has_smh:
+            r.s, r.m, r.h = op.smh
+        if has_flags:
+            r.flags = self.flags
+        fn = getattr(N.load(), f"cgp_{name}_{sfx}")
+        return lambda: N.check(fn(r, stream), "cgp_" + name)
 
     def _last_use(self, ops, extra_final):
         last = {}
@@ -972,17 +997,12 @@ class Plan:
                     a.weight, a.bias = g.weight, g.bias
                     N.check(getattr(N.load(), f"cgp_conv_{sfx}")(a, stream), "cgp_conv")
                 out = (buf[:n1], buf[n1:])
-            elif op.kind in ("relu", "erf", "gelu"):
+            elif op.kind in NONLIN_KINDS:
                 xin, yin = vals[op.src]
                 buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
                 N.call(f"cgp_var_{op.kind}_{sfx}", N.ptr(xin), N.ptr(yin), n1, n2, ho * wo,
-                       int(same), N.ptr(buf[:n1]), N.ptr(buf[n1:]), stream)
-                out = (buf[:n1], buf[n1:])
-            elif op.kind == "abrelu":
-                xin, yin = vals[op.src]
-                buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
-                N.call(f"cgp_var_abrelu_{sfx}", N.ptr(xin), N.ptr(yin), n1, n2, ho * wo,
-                       int(same), op.smh[2], N.ptr(buf[:n1]), N.ptr(buf[n1:]), stream)
+                       int(same), *NONLIN_CALLS[op.kind][4](op), N.ptr(buf[:n1]),
+                       N.ptr(buf[n1:]), stream)
                 out = (buf[:n1], buf[n1:])
             elif op.kind == "add":
                 buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
@@ -1196,30 +1216,11 @@ class Plan:
                 a.flags = self.flags
                 fn = getattr(lib, f"cgp_conv_{sfx}")
                 launch = (lambda fn=fn, a=a: N.check(fn(a, stream), "cgp_conv"))
-            elif op.kind == "relu":
+            elif op.kind in NONLIN_KINDS:
                 out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
-                vx, vy = var[op.src]
-                r = N.ReluArgs()
-                r.xy, r.out = N.ptr(vals[op.src]), N.ptr(out)
-                r.addend = N.ptr(vals[op.addend]) if op.addend is not None else None
-                r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                r.nmaps, r.n1, r.n2 = nmaps, n1, n2
-                r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
-                r.flags = self.flags
-                fn = getattr(lib, f"cgp_relu_{sfx}")
-                launch = (lambda fn=fn, r=r: N.check(fn(r, stream), "cgp_relu"))
-            elif op.kind in ("erf", "gelu", "abrelu"):
-                out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
-                vx, vy = var[op.src]
-                r = self._nonlin_args(op)
-                r.xy, r.out_xy = N.ptr(vals[op.src]), N.ptr(out)
-                r.addend = N.ptr(vals[op.addend]) if op.addend is not None else None
-                r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                r.nmaps, r.n1, r.n2 = nmaps, n1, n2
-                r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
-                fn = getattr(lib, f"cgp_{op.kind}_{sfx}")
-                launch = (lambda fn=fn, r=r, what="cgp_" + op.kind:
-                          N.check(fn(r, stream), what))
+                launch = self._nonlin_launch(
+                    op, sfx, stream, vals[op.src], out, var[op.src], n1, n2, same, diag,
+                    addend=vals[op.addend] if op.addend is not None else None)
             elif op.kind == "add":
                 out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
                 n = nmaps * ho * wo
@@ -1290,40 +1291,15 @@ class Plan:
                 a.weight, a.bias = g.weight, st.bias
                 a.flags = self.flags
                 N.check(getattr(lib, f"cgp_conv_{sfx}")(a, stream), "cgp_conv")
-            elif st.fn == "relu":
+            elif st.fn.removesuffix("_ntk") in NONLIN_KINDS:
                 out = bufs[st.dst] = new(op)
-                vx, vy = var[st.var]
-                r = N.ReluArgs()
-                r.xy, r.out, r.addend = N.ptr(bufs[st.src]), N.ptr(out), None
-                r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                r.nmaps, r.n1, r.n2 = nmaps, n1, n2
-                r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
-                r.flags = self.flags
-                N.check(getattr(lib, f"cgp_relu_{sfx}")(r, stream), "cgp_relu")
-            elif st.fn == "relu_ntk":
-                out = bufs[st.dst] = new(op)
-                tout = bufs[st.dst_theta] = new(op)
-                vx, vy = var[st.var]
-                r = N.ReluNtkArgs()
-                r.xy, r.theta = N.ptr(bufs[st.src]), N.ptr(bufs[st.theta])
-                r.out_xy, r.out_theta = N.ptr(out), N.ptr(tout)
-                r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                r.nmaps, r.n1, r.n2 = nmaps, n1, n2
-                r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
-                r.flags = self.flags
-                N.check(getattr(lib, f"cgp_relu_ntk_{sfx}")(r, stream), "cgp_relu_ntk")
-            elif st.fn in ("erf", "erf_ntk", "gelu", "gelu_ntk", "abrelu", "abrelu_ntk"):
-                out = bufs[st.dst] = new(op)
-                vx, vy = var[st.var]
-                r = self._nonlin_args(op)
-                r.xy, r.out_xy = N.ptr(bufs[st.src]), N.ptr(out)
-                if st.fn.endswith("_ntk"):
+                two = st.fn.endswith("_ntk")
+                tout = None
+                if two:
                     tout = bufs[st.dst_theta] = new(op)
-                    r.theta, r.out_theta = N.ptr(bufs[st.theta]), N.ptr(tout)
-                r.xx, r.yy = N.ptr(vx), N.ptr(vy)
-                r.nmaps, r.n1, r.n2 = nmaps, n1, n2
-                r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
-                N.check(getattr(lib, f"cgp_{op.kind}_{sfx}")(r, stream), "cgp_" + op.kind)
+                self._nonlin_launch(op, sfx, stream, bufs[st.src], out, var[st.var], n1, n2, same,
+                                    diag, theta=bufs[st.theta] if two else None,
+                                    out_theta=tout)()
             elif st.fn == "axpby":
                 out = bufs[st.dst] = new(op)
                 _axpby_terms(sfx, [(c, bufs[b]) for c, b in st.terms], out, nmaps * ho * wo,

@@ -17,6 +17,12 @@ int check_launch(const char* what);
 // compute units of the current device (cached; launch geometry of persistent kernels)
 int device_cus();
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+// grid of a grid-stride kernel of 256-thread workgroups over n elements
+inline unsigned grid_for(long long n) {
+    long long g = (n + 255) / 256;
+    if (g > 256 * 8 * 4) g = 256 * 8 * 4;   // ≈4 rounds of 8 blocks per CU, grid-stride rest
+    return (unsigned)(g < 1 ? 1 : g);
+}
 // the device that owns stream s (the current device for the null stream)
 inline hipError_t stream_device(hipStream_t s, int* dev) {
     if (s == nullptr) return hipGetDevice(dev);
@@ -40,10 +46,9 @@ inline hipError_t stream_device(hipStream_t s, int* dev) {
 // q = (umulhi(n, m) + n) >> s with s = ceil(log2 d), m = floor(2^32 (2^s - d) / d) + 1.
 //
 // The add is a 32-bit one: umulhi(n, m) <= n, so it is exact for n < 2^31 and may wrap
-// beyond.  cov_moments_kernel, cov_nonlin_kernel (covpool.hip), gelu_cov_kernel (gelu.hip) and
-// cov_nonlin_ntk_kernel (covntk.hip) divide r0 + e by (h·w)², with r0 < (h·w)² a chunk's
-// offset in its first pair and e < 2048: they rely on their files' kMaxPairElems = 2^30 for
-// r0 + e <= 2^30 + 2046 < 2^31.  The conv, avgpool and corrconv kernels divide indices into
+// beyond.  cov_moments_kernel (covpool.hip) and cov_walk_kernel (nonlin_walk.h) divide r0 + e
+// by (h·w)², with r0 < (h·w)² a chunk's offset in its first pair and e < 2048: they rely on
+// kMaxPairElems = 2^30 below for r0 + e <= 2^30 + 2046 < 2^31.  The conv, avgpool and corrconv kernels divide indices into
 // one workgroup's staged or written elements: at most 2^30, by the 64 KB of LDS it may take
 // and the same cap on one map.  cgp_selftest checks these divisors and numerators on the host.
 // ----------------------------------------------------------------------------------
@@ -648,8 +653,8 @@ __device__ __forceinline__ T relu_kdot(T c, T v1, T v2, int exact) {
 }
 
 // ----------------------------------------------------------------------------------
-// erf networks (include/cnngp.h): one function per stream, shared by every
-// caller.  One evaluation mode: correctly rounded division and square root, the device
+// erf networks (include/cnngp.h): the variance map; the pair map is ErfMap
+// (nonlin_walk.h).  One evaluation mode: correctly rounded division and square root, the device
 // library's atan; every op rounded in T.
 // ----------------------------------------------------------------------------------
 __device__ __forceinline__ double atan_t(double x) { return atan(x); }
@@ -674,22 +679,6 @@ __device__ __forceinline__ T erf_var(T v) {
     return erf_var(v, kdot);
 }
 
-// erf of pair map m at pixel px with the overrides of relu_pair; kdot = dK'/dc at fixed
-// variances (dead code where the caller drops it)
-template <typename T>
-__device__ __forceinline__ T erf_pair(T c, const T* __restrict__ xx, const T* __restrict__ yy,
-                                      unsigned i, unsigned j, int hw, int px, int same,
-                                      int diag, T& kdot) {
-    const T v1 = xx[(size_t)i * hw + px];
-    if (same && (diag || i == j)) return erf_var(v1, kdot);  // xy' = xx'
-    const T v2 = yy[(size_t)j * hw + px];
-    T d = T(1) + T(2) * (v1 + v2) + T(4) * (v1 * v2 - c * c);
-    d = d < T(1) ? T(1) : d;                                 // NaN kept
-    const T s = sqrt_t(d);
-    kdot = KErf<T>::four_over_pi / s;
-    return KErf<T>::two_over_pi * atan_t((T(2) * c) / s);
-}
-
 // pair index -> (i, j)
 __device__ __forceinline__ void pair_of(unsigned m, const FastDiv& n2, int diag, unsigned& i,
                                         unsigned& j) {
@@ -703,6 +692,10 @@ __device__ __forceinline__ void pair_of(unsigned m, const FastDiv& n2, int diag,
 
 // position-pair maps [pair][p_row][q_row][p_col][q_col] (include/cnngp.h): element of one
 // pair's map -> pixels p = p_row·w + p_col, q = q_row·w + q_col
+constexpr long long kMaxPairElems = 1LL << 30;   // (h·w)² of one pair: 32-bit index math
+inline bool bad_map(int h, int w) {
+    return h <= 0 || w <= 0 || (long long)h * w * h * w > kMaxPairElems;
+}
 struct CovIdx {
     FastDiv dn, dww, dh, dw;   // (h·w)², w², h, w
     int w;

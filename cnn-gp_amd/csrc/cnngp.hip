@@ -585,202 +585,6 @@ __global__ __launch_bounds__(kBlock) void conv_geo_kernel(const GeoP<T> p) {
     X(16, 16, 8, 8, 1, 2, 0)         \
     X(8, 8, 8, 8, 3, 1, -1)
 
-// ----------------------------------------------------------------------------------
-// standalone ReLU on pair maps (+ optional addend), one chunk of maps per workgroup
-// ----------------------------------------------------------------------------------
-template <typename T>
-struct ReluP {
-    const T* xy;
-    T* out;
-    const T* addend;
-    const T* xx;
-    const T* yy;
-    long long nmaps;
-    FastDiv n2, dhw;
-    int hw, same, diag, exact, mpb;
-};
-
-template <typename T, bool ADD>
-__global__ __launch_bounds__(kBlock) void relu_pair_kernel(const ReluP<T> p) {
-    const long long m0 = (long long)blockIdx.x * p.mpb;
-    long long rem = p.nmaps - m0;
-    const int mb = rem < p.mpb ? (int)rem : p.mpb;
-    const int n = mb * p.hw;
-    const T* src = p.xy + m0 * p.hw;
-    T* dst = p.out + m0 * p.hw;
-    const T* add = ADD ? p.addend + m0 * p.hw : nullptr;
-    T v[kEMax];
-#pragma unroll
-    for (int k = 0; k < kEMax; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        v[k] = e < n ? src[e] : T(0);
-    }
-#pragma unroll
-    for (int k = 0; k < kEMax; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        if (e < n) {
-            const unsigned ml = fdiv((unsigned)e, p.dhw);
-            const int px = e - (int)ml * p.hw;
-            unsigned i, j;
-            pair_of((unsigned)(m0 + ml), p.n2, p.diag, i, j);
-            T r = relu_pair(v[k], p.xx, p.yy, i, j, p.hw, px, p.same, p.diag, p.exact);
-            if constexpr (ADD) r = r + add[e];
-            dst[e] = r;
-        }
-    }
-}
-
-// ----------------------------------------------------------------------------------
-// ReLU of the NTK recursion on pair maps: K' = relu(K) exactly as relu_pair_kernel writes
-// it, and Theta' = Theta * kdot with kdot = (pi - theta)/(2 pi) the derivative of the
-// arc-cosine map in c at fixed variances, theta from the same t = v1 v2 + tiny as
-// kernels.py:146-151.  Where the reference overrides K' (same and i == j, or same and
-// diag) rho = 1 and Theta' = Theta/2 exactly.  One pass: 3 map reads (K, Theta and the
-// broadcast variances), 2 map writes; every element is read and written by one thread,
-// reads first, so the outputs may alias the inputs (and K may alias Theta).
-// ----------------------------------------------------------------------------------
-template <typename T>
-struct ReluNtkP {
-    const T* xy;
-    const T* theta;
-    T* out_xy;
-    T* out_theta;
-    const T* xx;
-    const T* yy;
-    long long nmaps;
-    FastDiv n2, dhw;
-    int hw, same, diag, exact, mpb;
-};
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void relu_ntk_kernel(const ReluNtkP<T> p) {
-    const long long m0 = (long long)blockIdx.x * p.mpb;
-    long long rem = p.nmaps - m0;
-    const int mb = rem < p.mpb ? (int)rem : p.mpb;
-    const int n = mb * p.hw;
-    const T* src = p.xy + m0 * p.hw;
-    const T* tsrc = p.theta + m0 * p.hw;
-    T* dst = p.out_xy + m0 * p.hw;
-    T* tdst = p.out_theta + m0 * p.hw;
-    T v[kEMax], th[kEMax];
-#pragma unroll
-    for (int k = 0; k < kEMax; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        v[k] = e < n ? src[e] : T(0);
-        th[k] = e < n ? tsrc[e] : T(0);
-    }
-#pragma unroll
-    for (int k = 0; k < kEMax; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        if (e < n) {
-            const unsigned ml = fdiv((unsigned)e, p.dhw);
-            const int px = e - (int)ml * p.hw;
-            unsigned i, j;
-            pair_of((unsigned)(m0 + ml), p.n2, p.diag, i, j);
-            const T r = relu_pair(v[k], p.xx, p.yy, i, j, p.hw, px, p.same, p.diag, p.exact);
-            T kd;
-            if (p.same && (p.diag || i == j))
-                kd = T(0.5);                                 // kdot at rho = 1
-            else
-                kd = relu_kdot(v[k], p.xx[(size_t)i * p.hw + px], p.yy[(size_t)j * p.hw + px],
-                               p.exact);
-            dst[e] = r;
-            tdst[e] = th[k] * kd;
-        }
-    }
-}
-
-// ReLU on the per-image variances (kernels.py:154-164)
-template <typename T>
-__global__ __launch_bounds__(kBlock) void var_relu_kernel(const T* __restrict__ xx,
-                                                          const T* __restrict__ yy,
-                                                          long long n_xx, long long n_yy,
-                                                          int same, T* xo, T* yo) {
-    const long long stride = (long long)gridDim.x * kBlock;
-    for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < n_xx + n_yy;
-         e += stride) {
-        if (e < n_xx) {
-            xo[e] = xx[e] / T(2);
-        } else {
-            const long long f = e - n_xx;
-            yo[f] = same ? xx[f] / T(2) : yy[f] / T(2);
-        }
-    }
-}
-
-// ----------------------------------------------------------------------------------
-// erf on pair maps (cgp_erf_*): relu_pair_kernel's chunking.  NTK: the second map Theta is
-// carried through the same pass, Theta' = Theta * kdot from the square root K' already paid
-// for.  Every element is read (all loads first) and written by one thread, so the outputs
-// may alias the inputs and Theta may alias K; no __restrict__ on the maps for that reason.
-// ----------------------------------------------------------------------------------
-template <typename T>
-struct ErfP {
-    const T* xy;
-    const T* theta;
-    T* out_xy;
-    T* out_theta;
-    const T* addend;
-    const T* xx;
-    const T* yy;
-    long long nmaps;
-    FastDiv n2, dhw;
-    int hw, same, diag, mpb;
-};
-
-template <typename T, bool NTK, bool ADD>
-__global__ __launch_bounds__(kBlock) void erf_pair_kernel(const ErfP<T> p) {
-    const long long m0 = (long long)blockIdx.x * p.mpb;
-    long long rem = p.nmaps - m0;
-    const int mb = rem < p.mpb ? (int)rem : p.mpb;
-    const int n = mb * p.hw;
-    const T* src = p.xy + m0 * p.hw;
-    const T* tsrc = NTK ? p.theta + m0 * p.hw : nullptr;
-    T* dst = p.out_xy + m0 * p.hw;
-    T* tdst = NTK ? p.out_theta + m0 * p.hw : nullptr;
-    const T* add = ADD ? p.addend + m0 * p.hw : nullptr;
-    T v[kEMax], th[NTK ? kEMax : 1];
-#pragma unroll
-    for (int k = 0; k < kEMax; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        v[k] = e < n ? src[e] : T(0);
-        if constexpr (NTK) th[k] = e < n ? tsrc[e] : T(0);
-    }
-#pragma unroll
-    for (int k = 0; k < kEMax; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        if (e < n) {
-            const unsigned ml = fdiv((unsigned)e, p.dhw);
-            const int px = e - (int)ml * p.hw;
-            unsigned i, j;
-            pair_of((unsigned)(m0 + ml), p.n2, p.diag, i, j);
-            T kd;
-            T r = erf_pair(v[k], p.xx, p.yy, i, j, p.hw, px, p.same, p.diag, kd);
-            if constexpr (ADD) r = r + add[e];
-            dst[e] = r;
-            if constexpr (NTK) tdst[e] = th[k] * kd;
-        }
-    }
-}
-
-// erf on the per-image variances
-template <typename T>
-__global__ __launch_bounds__(kBlock) void var_erf_kernel(const T* __restrict__ xx,
-                                                         const T* __restrict__ yy,
-                                                         long long n_xx, long long n_yy,
-                                                         int same, T* xo, T* yo) {
-    const long long stride = (long long)gridDim.x * kBlock;
-    for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < n_xx + n_yy;
-         e += stride) {
-        if (e < n_xx) {
-            xo[e] = erf_var(xx[e]);
-        } else {
-            const long long f = e - n_xx;
-            yo[f] = erf_var(same ? xx[f] : yy[f]);
-        }
-    }
-}
-
 // input moments, pair maps (kernels.py:44-47)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void moments_xy_kernel(const T* __restrict__ x,
@@ -1219,12 +1023,6 @@ __global__ __launch_bounds__(kBlock) void argmax_rows_kernel(const double* __res
 // host helpers
 // ----------------------------------------------------------------------------------
 
-inline unsigned grid_for(long long n) {
-    long long g = (n + kBlock - 1) / kBlock;
-    if (g > 256 * 8 * 4) g = 256 * 8 * 4;   // ≈4 rounds of 8 blocks per CU, grid-stride rest
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
 inline int maps_per_chunk(int hw, int requested) {
     if (requested > 0) return requested;
     int m = kChunkElems / hw;
@@ -1459,147 +1257,6 @@ int conv_impl(const cgp_conv_args* a, void* stream, int32_t* plan = nullptr) {
 }
 
 template <typename T>
-int relu_impl(const cgp_relu_args* a, void* stream) {
-    if (!a || !a->xy || !a->out || !a->xx)
-        return fail(CGP_EINVAL, "relu: NULL argument");
-    if (a->hw <= 0 || a->nmaps <= 0 || a->nmaps >= (1LL << 31))
-        return fail(CGP_EINVAL, "relu: bad sizes");
-    if (a->n1 <= 0 || a->n2 <= 0 || (a->diag ? a->n1 : a->n1 * a->n2) != a->nmaps)
-        return fail(CGP_EINVAL, "relu: nmaps inconsistent with n1/n2/diag");
-    if (a->diag && a->n1 != a->n2) return fail(CGP_EINVAL, "relu: diag needs n1 == n2");
-    if (!(a->same && a->diag) && !a->yy) return fail(CGP_EINVAL, "relu: yy is NULL");
-    ReluP<T> p;
-    p.xy = static_cast<const T*>(a->xy);
-    p.out = static_cast<T*>(a->out);
-    p.addend = static_cast<const T*>(a->addend);
-    p.xx = static_cast<const T*>(a->xx);
-    p.yy = static_cast<const T*>(a->yy);
-    p.nmaps = a->nmaps;
-    p.n2 = make_fastdiv((unsigned)a->n2);
-    p.dhw = make_fastdiv((unsigned)a->hw);
-    p.hw = a->hw;
-    p.same = a->same;
-    p.diag = a->diag;
-    p.exact = (a->flags & CGP_FLAG_EXACT_RELU) != 0;
-    // one chunk of whole maps per workgroup, at most kEMax elements per thread
-    p.mpb = std::max(1, kChunkElems / a->hw);
-    if (a->hw > kChunkElems) return fail(CGP_EINVAL, "relu: map of %d pixels too large", a->hw);
-    const long long blocks = (a->nmaps + p.mpb - 1) / p.mpb;
-    hipStream_t s = as_stream(stream);
-    if (a->addend)
-        hipLaunchKernelGGL((relu_pair_kernel<T, true>), dim3((unsigned)blocks), dim3(kBlock), 0,
-                           s, p);
-    else
-        hipLaunchKernelGGL((relu_pair_kernel<T, false>), dim3((unsigned)blocks), dim3(kBlock),
-                           0, s, p);
-    return check_launch("relu_pair_kernel");
-}
-
-template <typename T>
-int relu_ntk_impl(const cgp_relu_ntk_args* a, void* stream) {
-    if (!a || !a->xy || !a->theta || !a->out_xy || !a->out_theta || !a->xx)
-        return fail(CGP_EINVAL, "relu_ntk: NULL argument");
-    if (a->hw <= 0 || a->nmaps <= 0 || a->nmaps >= (1LL << 31))
-        return fail(CGP_EINVAL, "relu_ntk: bad sizes");
-    if (a->n1 <= 0 || a->n2 <= 0 || (a->diag ? a->n1 : a->n1 * a->n2) != a->nmaps)
-        return fail(CGP_EINVAL, "relu_ntk: nmaps inconsistent with n1/n2/diag");
-    if ((a->same || a->diag) && a->n1 != a->n2)
-        return fail(CGP_EINVAL, "relu_ntk: same / diag need n1 == n2");
-    if (!(a->same && a->diag) && !a->yy) return fail(CGP_EINVAL, "relu_ntk: yy is NULL");
-    if (a->hw > kChunkElems)
-        return fail(CGP_EINVAL, "relu_ntk: map of %d pixels too large", a->hw);
-    ReluNtkP<T> p;
-    p.xy = static_cast<const T*>(a->xy);
-    p.theta = static_cast<const T*>(a->theta);
-    p.out_xy = static_cast<T*>(a->out_xy);
-    p.out_theta = static_cast<T*>(a->out_theta);
-    p.xx = static_cast<const T*>(a->xx);
-    p.yy = static_cast<const T*>(a->yy);
-    p.nmaps = a->nmaps;
-    p.n2 = make_fastdiv((unsigned)a->n2);
-    p.dhw = make_fastdiv((unsigned)a->hw);
-    p.hw = a->hw;
-    p.same = a->same;
-    p.diag = a->diag;
-    p.exact = (a->flags & CGP_FLAG_EXACT_RELU) != 0;
-    // relu_impl's chunking: whole maps per workgroup, at most kEMax elements per thread
-    p.mpb = std::max(1, kChunkElems / a->hw);
-    const long long blocks = (a->nmaps + p.mpb - 1) / p.mpb;
-    hipLaunchKernelGGL((relu_ntk_kernel<T>), dim3((unsigned)blocks), dim3(kBlock), 0,
-                       as_stream(stream), p);
-    return check_launch("relu_ntk_kernel");
-}
-
-template <typename T, bool NTK>
-int launch_erf(const ErfP<T>& p, long long blocks, hipStream_t s) {
-    if (p.addend)
-        hipLaunchKernelGGL((erf_pair_kernel<T, NTK, true>), dim3((unsigned)blocks),
-                           dim3(kBlock), 0, s, p);
-    else
-        hipLaunchKernelGGL((erf_pair_kernel<T, NTK, false>), dim3((unsigned)blocks),
-                           dim3(kBlock), 0, s, p);
-    return check_launch("erf_pair_kernel");
-}
-
-template <typename T>
-int erf_impl(const cgp_erf_args* a, void* stream) {
-    // relu_ntk_impl's checks; theta == NULL is the forward-only form
-    if (!a || !a->xy || !a->out_xy || !a->xx || (a->theta && !a->out_theta))
-        return fail(CGP_EINVAL, "erf: NULL argument");
-    if (a->hw <= 0 || a->nmaps <= 0 || a->nmaps >= (1LL << 31))
-        return fail(CGP_EINVAL, "erf: bad sizes");
-    if (a->n1 <= 0 || a->n2 <= 0 || (a->diag ? a->n1 : a->n1 * a->n2) != a->nmaps)
-        return fail(CGP_EINVAL, "erf: nmaps inconsistent with n1/n2/diag");
-    if ((a->same || a->diag) && a->n1 != a->n2)
-        return fail(CGP_EINVAL, "erf: same / diag need n1 == n2");
-    if (!(a->same && a->diag) && !a->yy) return fail(CGP_EINVAL, "erf: yy is NULL");
-    if (a->hw > kChunkElems) return fail(CGP_EINVAL, "erf: map of %d pixels too large", a->hw);
-    ErfP<T> p;
-    p.xy = static_cast<const T*>(a->xy);
-    p.theta = static_cast<const T*>(a->theta);
-    p.out_xy = static_cast<T*>(a->out_xy);
-    p.out_theta = static_cast<T*>(a->out_theta);
-    p.addend = static_cast<const T*>(a->addend);
-    p.xx = static_cast<const T*>(a->xx);
-    p.yy = static_cast<const T*>(a->yy);
-    p.nmaps = a->nmaps;
-    p.n2 = make_fastdiv((unsigned)a->n2);
-    p.dhw = make_fastdiv((unsigned)a->hw);
-    p.hw = a->hw;
-    p.same = a->same;
-    p.diag = a->diag;
-    // relu_impl's chunking: whole maps per workgroup, at most kEMax elements per thread
-    p.mpb = std::max(1, kChunkElems / a->hw);
-    const long long blocks = (a->nmaps + p.mpb - 1) / p.mpb;
-    hipStream_t s = as_stream(stream);
-    return a->theta ? launch_erf<T, true>(p, blocks, s) : launch_erf<T, false>(p, blocks, s);
-}
-
-template <typename T>
-int var_erf_impl(const T* xx, const T* yy, int64_t n1, int64_t n2, int32_t hw, int32_t same,
-                 T* xo, T* yo, void* stream) {
-    if (!xx || !yy || !xo || !yo) return fail(CGP_EINVAL, "var_erf: NULL argument");
-    if (n1 <= 0 || n2 <= 0 || hw <= 0) return fail(CGP_EINVAL, "var_erf: bad sizes");
-    if (same && n1 != n2) return fail(CGP_EINVAL, "var_erf: same needs n1 == n2");
-    const long long nx = n1 * hw, ny = n2 * hw;
-    hipLaunchKernelGGL((var_erf_kernel<T>), dim3(grid_for(nx + ny)), dim3(kBlock), 0,
-                       as_stream(stream), xx, yy, nx, ny, same, xo, yo);
-    return check_launch("var_erf_kernel");
-}
-
-template <typename T>
-int var_relu_impl(const T* xx, const T* yy, int64_t n1, int64_t n2, int32_t hw, int32_t same,
-                  T* xo, T* yo, void* stream) {
-    if (!xx || !yy || !xo || !yo) return fail(CGP_EINVAL, "var_relu: NULL argument");
-    if (n1 <= 0 || n2 <= 0 || hw <= 0) return fail(CGP_EINVAL, "var_relu: bad sizes");
-    if (same && n1 != n2) return fail(CGP_EINVAL, "var_relu: same needs n1 == n2");
-    const long long nx = n1 * hw, ny = n2 * hw;
-    hipLaunchKernelGGL((var_relu_kernel<T>), dim3(grid_for(nx + ny)), dim3(kBlock), 0,
-                       as_stream(stream), xx, yy, nx, ny, same, xo, yo);
-    return check_launch("var_relu_kernel");
-}
-
-template <typename T>
 int moments_xy_impl(const T* x, const T* y, int64_t n1, int64_t n2, int32_t c, int32_t hw,
                     int32_t diag, T* xy, void* stream) {
     if (!x || !y || !xy) return fail(CGP_EINVAL, "moments_xy: NULL argument");
@@ -1772,9 +1429,6 @@ int cgp_abi_version(void) { return CGP_ABI_VERSION; }
 double cgp_net_xvar_scale(void) { return kXVarScale; }
 const char* cgp_last_error(void) { return g_last_error.c_str(); }
 size_t cgp_conv_args_size(void) { return sizeof(cgp_conv_args); }
-size_t cgp_relu_args_size(void) { return sizeof(cgp_relu_args); }
-size_t cgp_relu_ntk_args_size(void) { return sizeof(cgp_relu_ntk_args); }
-size_t cgp_erf_args_size(void) { return sizeof(cgp_erf_args); }
 size_t cgp_var_op_size(void) { return sizeof(cgp_var_op); }
 size_t cgp_var_args_size(void) { return sizeof(cgp_var_args); }
 int cgp_var_chain_f64(const cgp_var_args* a, void* stream) { return var_chain_impl<double>(a, stream); }
@@ -1843,40 +1497,6 @@ int cgp_conv_plan_f64(const cgp_conv_args* args, int32_t out[4]) {
 int cgp_conv_plan_f32(const cgp_conv_args* args, int32_t out[4]) {
     if (!out) return fail(CGP_EINVAL, "conv plan: out is NULL");
     return conv_impl<float>(args, nullptr, out);
-}
-int cgp_relu_f64(const cgp_relu_args* args, void* stream) {
-    return relu_impl<double>(args, stream);
-}
-int cgp_relu_f32(const cgp_relu_args* args, void* stream) {
-    return relu_impl<float>(args, stream);
-}
-int cgp_relu_ntk_f64(const cgp_relu_ntk_args* args, void* stream) {
-    return relu_ntk_impl<double>(args, stream);
-}
-int cgp_relu_ntk_f32(const cgp_relu_ntk_args* args, void* stream) {
-    return relu_ntk_impl<float>(args, stream);
-}
-int cgp_erf_f64(const cgp_erf_args* args, void* stream) {
-    return erf_impl<double>(args, stream);
-}
-int cgp_erf_f32(const cgp_erf_args* args, void* stream) {
-    return erf_impl<float>(args, stream);
-}
-int cgp_var_erf_f64(const double* xx, const double* yy, int64_t n1, int64_t n2, int32_t hw,
-                    int32_t same, double* xo, double* yo, void* stream) {
-    return var_erf_impl<double>(xx, yy, n1, n2, hw, same, xo, yo, stream);
-}
-int cgp_var_erf_f32(const float* xx, const float* yy, int64_t n1, int64_t n2, int32_t hw,
-                    int32_t same, float* xo, float* yo, void* stream) {
-    return var_erf_impl<float>(xx, yy, n1, n2, hw, same, xo, yo, stream);
-}
-int cgp_var_relu_f64(const double* xx, const double* yy, int64_t n1, int64_t n2, int32_t hw,
-                     int32_t same, double* xo, double* yo, void* stream) {
-    return var_relu_impl<double>(xx, yy, n1, n2, hw, same, xo, yo, stream);
-}
-int cgp_var_relu_f32(const float* xx, const float* yy, int64_t n1, int64_t n2, int32_t hw,
-                     int32_t same, float* xo, float* yo, void* stream) {
-    return var_relu_impl<float>(xx, yy, n1, n2, hw, same, xo, yo, stream);
 }
 int cgp_axpby_f64(double alpha, const double* a, double beta, const double* b, double* out,
                   int64_t n, void* stream) {

@@ -39,7 +39,6 @@ namespace {
 
 constexpr int kMaxUnits = 256;                // row pairs one workgroup may hold
 constexpr int kMaxLds = 64 * 1024;            // bytes of LDS one workgroup may take
-constexpr long long kMaxPairElems = 1LL << 30;   // (h·w)² of one pair: 32-bit index math
 
 // offset pairs the 1024-thread instantiation carries at a time (their block offsets and
 // weights stay in scalar registers: 16 pairs spill them, and measured no faster)

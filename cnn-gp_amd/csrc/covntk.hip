@@ -16,8 +16,7 @@
 #include <algorithm>
 
 #include "cnngp.h"
-#include "cgp_common.h"
-#include "gelu_math.h"
+#include "nonlin_walk.h"
 
 using namespace cgp;
 
@@ -29,103 +28,9 @@ constexpr int kE = kChunk / kBlock;           // loads in flight per thread and 
 constexpr int kMaxUnits = 256;                // row pairs one conv workgroup may hold
 constexpr int kMaxBlocks = 1024;              // blocks (row pairs x taps) of one stream it may stage
 constexpr int kMaxLds = 64 * 1024;            // bytes of LDS one conv workgroup may take
-constexpr long long kMaxPairElems = 1LL << 30;   // (h·w)² of one pair: 32-bit index math
 
-// The nonlinearity's map of (c, v1, v2) = (S[p, q], xx_i[p], yy_j[q]) and its κ̇ = dK'/dc at
-// fixed variances, with the device functions of the layer kernels.  Where the two arguments
-// are one pre-activation (same, i == j and p == q) the map is the variance map's value and κ̇
-// the layer path's override: 1/2, (4/π)/√(1 + 4v), the GELU line at c = v1 = v2 = v.
-template <typename T>
-__device__ __forceinline__ T cov_nonlin_ntk(T c, int kind, const T* __restrict__ xx,
-                                            const T* __restrict__ yy, int i, int j, int hw,
-                                            int p, int q, int same, int exact, T& kdot) {
-    const T* vx = xx + (size_t)i * hw + p;
-    const T* vy = yy + (size_t)j * hw + q;
-    const bool self = same && i == j && p == q;
-    if (kind == CGP_COV_RELU) {
-        const T v1 = *vx;
-        if (self) {
-            kdot = T(0.5);                                   // kdot at rho = 1
-            return v1 / T(2);
-        }
-        const T v2 = *vy;
-        kdot = relu_kdot(c, v1, v2, exact);
-        return exact ? relu_exact(c, v1, v2) : relu_fast(c, v1, v2);
-    }
-    if (kind == CGP_COV_ERF)
-        // erf_pair reads xx[i·hw + px] and yy[j·hw + px]: called at the two pixels' own addresses
-        return erf_pair(c, vx, self ? vx : vy, 0u, 0u, 0, 0, self ? 1 : 0, 0, kdot);
-    return gelu_pair(c, vx, self ? vx : vy, self, kdot);
-}
-
-bool bad_map(int h, int w) {
-    return h <= 0 || w <= 0 || (long long)h * w * h * w > kMaxPairElems;
-}
 bool is_nonlin(int kind) {
     return kind == CGP_COV_RELU || kind == CGP_COV_ERF || kind == CGP_COV_GELU;
-}
-
-// ----------------------------------------------------------------------------------
-// the nonlinearity step: cov_nonlin_kernel's shape with two streams, one 2048-element chunk
-// per workgroup, the loads of both streams issued before the math.  Every element is read
-// and written by one thread, so the outputs may be the inputs and theta may be in.
-// ----------------------------------------------------------------------------------
-template <typename T>
-struct NonlinNtkP {
-    const T* in;
-    const T* theta;
-    T* out;
-    T* out_theta;
-    const T* addend;
-    const T* addend_theta;
-    const T* xx;
-    const T* yy;
-    const int* pi;
-    const int* pj;
-    long long total;
-    CovIdx g;
-    int hw, kind, same, exact;
-};
-
-template <typename T, bool ADD>
-__global__ __launch_bounds__(kBlock) void cov_nonlin_ntk_kernel(const NonlinNtkP<T> p) {
-    const long long base = (long long)blockIdx.x * kChunk;
-    const long long rem = p.total - base;
-    const int n = rem < kChunk ? (int)rem : kChunk;
-    const long long m0 = base / p.g.dn.d;
-    const unsigned r0 = (unsigned)(base - m0 * p.g.dn.d);
-    const T* src = p.in + base;
-    const T* tsrc = p.theta + base;
-    T* dst = p.out + base;
-    T* tdst = p.out_theta + base;
-    T v[kE], th[kE];
-#pragma unroll
-    for (int k = 0; k < kE; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        v[k] = e < n ? src[e] : T(0);
-        th[k] = e < n ? tsrc[e] : T(0);
-    }
-#pragma unroll
-    for (int k = 0; k < kE; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        if (e < n) {
-            const unsigned rt = r0 + (unsigned)e;
-            const unsigned mm = fdiv(rt, p.g.dn);
-            const long long m = m0 + mm;
-            int px, qx;
-            cov_decode(p.g, rt - mm * p.g.dn.d, px, qx);
-            T kd;
-            T r = cov_nonlin_ntk(v[k], p.kind, p.xx, p.yy, p.pi[m], p.pj[m], p.hw, px, qx,
-                                 p.same, p.exact, kd);
-            T t = th[k] * kd;
-            if constexpr (ADD) {
-                if (p.addend) r = r + p.addend[base + e];
-                if (p.addend_theta) t = t + p.addend_theta[base + e];
-            }
-            dst[e] = r;
-            tdst[e] = t;
-        }
-    }
 }
 
 // ----------------------------------------------------------------------------------
@@ -255,9 +160,9 @@ __global__ __launch_bounds__(kBlock) void cov_conv_ntk_kernel(const CovConvNtkP<
         if (p.post != CGP_COV_NONE) {
             const int m = s_m[ul];
             T kd;
-            val = cov_nonlin_ntk(val, p.post, p.xx, p.yy, p.pi[m], p.pj[m], p.ho * p.wo,
-                                 s_pr[ul] * p.wo + (int)pc, s_qr[ul] * p.wo + qc, p.same,
-                                 p.exact, kd);
+            val = cov_nonlin<T, true>(val, p.post, p.xx, p.yy, p.pi[m], p.pj[m], p.ho * p.wo,
+                                      s_pr[ul] * p.wo + (int)pc, s_qr[ul] * p.wo + qc, p.same,
+                                      p.exact, kd);
             tval = tval * kd;
         }
         const long long oe = (u0 + ul) * wowo + o;
@@ -271,47 +176,6 @@ __global__ __launch_bounds__(kBlock) void cov_conv_ntk_kernel(const CovConvNtkP<
 // ----------------------------------------------------------------------------------
 // host side: every check returns CGP_EINVAL before any launch
 // ----------------------------------------------------------------------------------
-template <typename T>
-int cov_nonlin_ntk_impl(const cgp_covntk_nonlin_args* a, void* stream) {
-    if (!a || !a->in || !a->theta || !a->out || !a->out_theta || !a->xx || !a->yy ||
-        !a->pair_i || !a->pair_j)
-        return fail(CGP_EINVAL, "cov_nonlin_ntk: NULL argument");
-    if (a->out == a->out_theta)
-        return fail(CGP_EINVAL, "cov_nonlin_ntk: out and out_theta are one buffer");
-    if (a->npairs <= 0 || a->npairs >= (1LL << 31) || bad_map(a->h, a->w))
-        return fail(CGP_EINVAL, "cov_nonlin_ntk: bad sizes");
-    if (!is_nonlin(a->kind))
-        return fail(CGP_EINVAL, "cov_nonlin_ntk: kind %d is neither ReLU, erf nor GELU", a->kind);
-    NonlinNtkP<T> p;
-    p.in = static_cast<const T*>(a->in);
-    p.theta = static_cast<const T*>(a->theta);
-    p.out = static_cast<T*>(a->out);
-    p.out_theta = static_cast<T*>(a->out_theta);
-    p.addend = static_cast<const T*>(a->addend);
-    p.addend_theta = static_cast<const T*>(a->addend_theta);
-    p.xx = static_cast<const T*>(a->xx);
-    p.yy = static_cast<const T*>(a->yy);
-    p.pi = a->pair_i;
-    p.pj = a->pair_j;
-    p.total = (long long)a->npairs * a->h * a->w * a->h * a->w;
-    p.g = make_idx(a->h, a->w);
-    p.hw = a->h * a->w;
-    p.kind = a->kind;
-    p.same = a->same != 0;
-    p.exact = (a->flags & CGP_FLAG_EXACT_RELU) != 0;
-    const long long blocks = (p.total + kChunk - 1) / kChunk;
-    if (blocks >= (1LL << 31))
-        return fail(CGP_EINVAL, "cov_nonlin_ntk: %lld elements", p.total);
-    hipStream_t s = as_stream(stream);
-    if (a->addend || a->addend_theta)
-        hipLaunchKernelGGL((cov_nonlin_ntk_kernel<T, true>), dim3((unsigned)blocks),
-                           dim3(kBlock), 0, s, p);
-    else
-        hipLaunchKernelGGL((cov_nonlin_ntk_kernel<T, false>), dim3((unsigned)blocks),
-                           dim3(kBlock), 0, s, p);
-    return check_launch("cov_nonlin_ntk_kernel");
-}
-
 template <typename T>
 int cov_conv_ntk_impl(const cgp_covntk_conv_args* a, void* stream) {
     if (!a || !a->in || !a->out || !a->out_theta)
@@ -388,15 +252,8 @@ int cov_conv_ntk_impl(const cgp_covntk_conv_args* a, void* stream) {
 
 extern "C" {
 
-size_t cgp_covntk_nonlin_args_size(void) { return sizeof(cgp_covntk_nonlin_args); }
 size_t cgp_covntk_conv_args_size(void) { return sizeof(cgp_covntk_conv_args); }
 
-int cgp_covntk_nonlin_f64(const cgp_covntk_nonlin_args* args, void* stream) {
-    return cov_nonlin_ntk_impl<double>(args, stream);
-}
-int cgp_covntk_nonlin_f32(const cgp_covntk_nonlin_args* args, void* stream) {
-    return cov_nonlin_ntk_impl<float>(args, stream);
-}
 int cgp_covntk_conv_f64(const cgp_covntk_conv_args* args, void* stream) {
     return cov_conv_ntk_impl<double>(args, stream);
 }

@@ -18,7 +18,7 @@
 #include <algorithm>
 
 #include "cnngp.h"
-#include "cgp_common.h"
+#include "nonlin_walk.h"
 
 using namespace cgp;
 
@@ -31,28 +31,6 @@ constexpr int kMaxUnits = 256;                // row pairs one conv workgroup ma
 constexpr int kMaxBlocks = 1024;              // blocks (row pairs x taps) it may stage
 constexpr int kPoolBlock = 1024;              // threads of a pool workgroup (one per pair)
 constexpr int kMaxLds = 64 * 1024;            // bytes of LDS one conv workgroup may take
-constexpr long long kMaxPairElems = 1LL << 30;   // (h·w)² of one pair: 32-bit index math
-
-// The nonlinearity's map of (c, v1, v2) = (S[p, q], xx_i[p], yy_j[q]) with the device
-// functions of the layer kernels.  The reference's override (kernels.py:155-162) applies
-// where the two arguments are the same pre-activation: same, i == j and p == q.
-template <typename T>
-__device__ __forceinline__ T cov_nonlin(T c, int kind, const T* __restrict__ xx,
-                                        const T* __restrict__ yy, int i, int j, int hw, int p,
-                                        int q, int same, int exact) {
-    const T* vx = xx + (size_t)i * hw + p;
-    const T* vy = yy + (size_t)j * hw + q;
-    const bool self = same && i == j && p == q;
-    if (kind == CGP_COV_RELU) {
-        const T v1 = *vx;
-        if (self) return v1 / T(2);
-        const T v2 = *vy;
-        return exact ? relu_exact(c, v1, v2) : relu_fast(c, v1, v2);
-    }
-    // erf_pair reads xx[i·hw + px] and yy[j·hw + px]: called at the two pixels' own addresses
-    T kdot;
-    return erf_pair(c, vx, self ? vx : vy, 0u, 0u, 0, 0, self ? 1 : 0, 0, kdot);
-}
 
 // ----------------------------------------------------------------------------------
 // input moments: S[m][p, q] = mean_c x_i[c, p]·y_j[c, q], summed like moments_var_kernel
@@ -81,58 +59,6 @@ __global__ __launch_bounds__(kBlock) void cov_moments_kernel(const T* __restrict
         T acc = xi[0] * yj[0];
         for (int k = 1; k < c; ++k) acc += xi[(size_t)k * hw] * yj[(size_t)k * hw];
         out[base + e] = acc / T(c);
-    }
-}
-
-// ----------------------------------------------------------------------------------
-// standalone ReLU / erf (+ addend): relu_pair_kernel's shape, one 2048-element chunk per
-// workgroup, loads issued before the math.  Every element is read and written by one
-// thread, so out may be in.
-// ----------------------------------------------------------------------------------
-template <typename T>
-struct NonlinP {
-    const T* in;
-    T* out;
-    const T* addend;
-    const T* xx;
-    const T* yy;
-    const int* pi;
-    const int* pj;
-    long long total;
-    CovIdx g;
-    int hw, kind, same, exact;
-};
-
-template <typename T, bool ADD>
-__global__ __launch_bounds__(kBlock) void cov_nonlin_kernel(const NonlinP<T> p) {
-    const long long base = (long long)blockIdx.x * kChunk;
-    const long long rem = p.total - base;
-    const int n = rem < kChunk ? (int)rem : kChunk;
-    const long long m0 = base / p.g.dn.d;
-    const unsigned r0 = (unsigned)(base - m0 * p.g.dn.d);
-    const T* src = p.in + base;
-    const T* add = ADD ? p.addend + base : nullptr;
-    T* dst = p.out + base;
-    T v[kE];
-#pragma unroll
-    for (int k = 0; k < kE; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        v[k] = e < n ? src[e] : T(0);
-    }
-#pragma unroll
-    for (int k = 0; k < kE; ++k) {
-        const int e = threadIdx.x + k * kBlock;
-        if (e < n) {
-            const unsigned rt = r0 + (unsigned)e;
-            const unsigned mm = fdiv(rt, p.g.dn);
-            const long long m = m0 + mm;
-            int px, qx;
-            cov_decode(p.g, rt - mm * p.g.dn.d, px, qx);
-            T r = cov_nonlin(v[k], p.kind, p.xx, p.yy, p.pi[m], p.pj[m], p.hw, px, qx, p.same,
-                             p.exact);
-            if constexpr (ADD) r = r + add[e];
-            dst[e] = r;
-        }
     }
 }
 
@@ -243,9 +169,12 @@ __global__ __launch_bounds__(kBlock) void cov_conv_kernel(const CovConvP<T> p) {
         }
         T val = p.weight * acc + p.bias;
         const int m = s_m[ul];
-        if (p.post != CGP_COV_NONE)
-            val = cov_nonlin(val, p.post, p.xx, p.yy, p.pi[m], p.pj[m], p.ho * p.wo,
-                             s_pr[ul] * p.wo + (int)pc, s_qr[ul] * p.wo + qc, p.same, p.exact);
+        if (p.post != CGP_COV_NONE) {
+            T kd;
+            val = cov_nonlin<T, false>(val, p.post, p.xx, p.yy, p.pi[m], p.pj[m], p.ho * p.wo,
+                                       s_pr[ul] * p.wo + (int)pc, s_qr[ul] * p.wo + qc, p.same,
+                                       p.exact, kd);
+        }
         const long long oe = (u0 + ul) * wowo + o;
         if constexpr (ADD) val = val + p.addend[oe];
         p.out[oe] = val;
@@ -428,10 +357,6 @@ __global__ __launch_bounds__(kBlock) void cov_diag_kernel(const T* __restrict__ 
 // ----------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------
-bool bad_map(int h, int w) {
-    return h <= 0 || w <= 0 || (long long)h * w * h * w > kMaxPairElems;
-}
-
 template <typename T>
 int cov_moments_impl(const T* x, const T* y, const int32_t* pi, const int32_t* pj,
                      int64_t npairs, int32_t c, int32_t h, int32_t w, T* out, void* stream) {
@@ -444,40 +369,6 @@ int cov_moments_impl(const T* x, const T* y, const int32_t* pi, const int32_t* p
     hipLaunchKernelGGL((cov_moments_kernel<T>), dim3((unsigned)blocks), dim3(kBlock), 0,
                        as_stream(stream), x, y, pi, pj, total, make_idx(h, w), c, h * w, out);
     return check_launch("cov_moments_kernel");
-}
-
-template <typename T>
-int cov_nonlin_impl(const cgp_cov_nonlin_args* a, void* stream) {
-    if (!a || !a->in || !a->out || !a->xx || !a->yy || !a->pair_i || !a->pair_j)
-        return fail(CGP_EINVAL, "cov_nonlin: NULL argument");
-    if (a->npairs <= 0 || a->npairs >= (1LL << 31) || bad_map(a->h, a->w))
-        return fail(CGP_EINVAL, "cov_nonlin: bad sizes");
-    if (a->kind != CGP_COV_RELU && a->kind != CGP_COV_ERF)
-        return fail(CGP_EINVAL, "cov_nonlin: kind %d is neither ReLU nor erf", a->kind);
-    NonlinP<T> p;
-    p.in = static_cast<const T*>(a->in);
-    p.out = static_cast<T*>(a->out);
-    p.addend = static_cast<const T*>(a->addend);
-    p.xx = static_cast<const T*>(a->xx);
-    p.yy = static_cast<const T*>(a->yy);
-    p.pi = a->pair_i;
-    p.pj = a->pair_j;
-    p.total = (long long)a->npairs * a->h * a->w * a->h * a->w;
-    p.g = make_idx(a->h, a->w);
-    p.hw = a->h * a->w;
-    p.kind = a->kind;
-    p.same = a->same != 0;
-    p.exact = (a->flags & CGP_FLAG_EXACT_RELU) != 0;
-    const long long blocks = (p.total + kChunk - 1) / kChunk;
-    if (blocks >= (1LL << 31)) return fail(CGP_EINVAL, "cov_nonlin: %lld elements", p.total);
-    hipStream_t s = as_stream(stream);
-    if (a->addend)
-        hipLaunchKernelGGL((cov_nonlin_kernel<T, true>), dim3((unsigned)blocks), dim3(kBlock), 0,
-                           s, p);
-    else
-        hipLaunchKernelGGL((cov_nonlin_kernel<T, false>), dim3((unsigned)blocks), dim3(kBlock),
-                           0, s, p);
-    return check_launch("cov_nonlin_kernel");
 }
 
 template <typename T>
@@ -624,7 +515,6 @@ int cov_diag_impl(const T* in, const int32_t* pi, int64_t npairs, int32_t h, int
 extern "C" {
 
 size_t cgp_cov_conv_args_size(void) { return sizeof(cgp_cov_conv_args); }
-size_t cgp_cov_nonlin_args_size(void) { return sizeof(cgp_cov_nonlin_args); }
 
 int cgp_cov_moments_f64(const double* x, const double* y, const int32_t* pair_i,
                         const int32_t* pair_j, int64_t npairs, int32_t c, int32_t h, int32_t w,
@@ -641,12 +531,6 @@ int cgp_cov_conv_f64(const cgp_cov_conv_args* args, void* stream) {
 }
 int cgp_cov_conv_f32(const cgp_cov_conv_args* args, void* stream) {
     return cov_conv_impl<float>(args, stream);
-}
-int cgp_cov_nonlin_f64(const cgp_cov_nonlin_args* args, void* stream) {
-    return cov_nonlin_impl<double>(args, stream);
-}
-int cgp_cov_nonlin_f32(const cgp_cov_nonlin_args* args, void* stream) {
-    return cov_nonlin_impl<float>(args, stream);
 }
 int cgp_cov_pool_f64(const double* in, int64_t npairs, int64_t n, double* out, void* stream) {
     return cov_pool_impl<double>(in, npairs, n, out, stream);

@@ -1,7 +1,7 @@
 // gelu_math.h — the device functions of the GELU layer kernel (include/cnngp.h "The GELU
-// nonlinearity").  Included by gelu.hip only: one function per stream, shared
-// by the layer-path, the variance and the position-pair kernels, so the overridden K' of a
-// pair and the variance entry point's output are the same bits.
+// nonlinearity"), GeluMap's arithmetic (nonlin_walk.h): one function per stream,
+// shared by the layer-path, the variance and the position-pair walks, so the overridden K' of
+// a pair and the variance entry point's output are the same bits.
 //
 // phi(x) = x·Phi(x), the exact GELU.  For (u1, u2) ~ N(0, [[v1, c], [c, v2]]), with
 // P = v1 v2, P1 = (1 + v1)(1 + v2), D2 = P1 - c², D = sqrt(D2), t = c/D, a = atan(t)

@@ -1,0 +1,286 @@
+// nonlin_walk.h — the one element walk of every nonlinearity kernel.
+//
+// A nonlinearity is a map type F with two members,
+//   template <bool NTK> T pair(T c, const T* vx, const T* vy, bool self, T& kdot) const
+//   T var(T v) const
+// pair: K' of one pixel with covariance c and variances *vx, *vy, and with NTK its
+// κ̇ = dK'/dc at fixed variances (kdot is not written without NTK).  `self`: the two arguments
+// are one pre-activation (the reference's override, kernels.py:155-162): K' is var(*vx) and
+// vy is not read, so it may be any address.  var: the per-image variance map.
+//
+// Three kernels walk the elements and call the map:
+//   pair_walk_kernel  the layer path: pair maps [nmaps][hw], whole maps per workgroup
+//   cov_walk_kernel   position-pair maps [pair][p_row][q_row][p_col][q_col], one chunk per
+//                     workgroup, which may straddle pairs
+//   var_walk_kernel   the per-image variances, grid-stride
+// A workgroup takes at most 2048 elements, 8 per thread, and all of a thread's loads of K and
+// of Θ are issued before its math; the small variance maps are read through L2.  Every
+// element is read and written by one thread, so the outputs may alias the inputs and Θ may
+// alias K: no __restrict__ on the maps for that reason.  An addend is added after the map, a
+// rounding of its own.  nonlin.hip holds the entry points; covpool.hip and covntk.hip use
+// cov_nonlin() below for the post-stages of their conv kernels.
+#pragma once
+
+#include "cgp_common.h"
+#include "gelu_math.h"
+
+namespace cgp {
+
+constexpr int kWalkBlock = 256;                        // 4 waves of 64
+constexpr int kWalkChunk = 2048;                       // elements of one workgroup
+constexpr int kWalkE = kWalkChunk / kWalkBlock;        // loads in flight per thread and stream (8)
+
+// ----------------------------------------------------------------------------------
+// the maps
+// ----------------------------------------------------------------------------------
+
+// the ReLU map R and its κ̇ of two distinct pre-activations (cgp_common.h's functions)
+template <typename T, bool NTK>
+__device__ __forceinline__ T relu_elem(T c, T v1, T v2, int exact, T& kdot) {
+    const T r = exact ? relu_exact(c, v1, v2) : relu_fast(c, v1, v2);
+    if constexpr (NTK) kdot = relu_kdot(c, v1, v2, exact);
+    return r;
+}
+
+template <typename T>
+struct ReluMap {
+    int exact;   // CGP_FLAG_EXACT_RELU
+    template <bool NTK>
+    __device__ __forceinline__ T pair(T c, const T* vx, const T* vy, bool self, T& kdot) const {
+        const T v1 = *vx;
+        if (self) {
+            if constexpr (NTK) kdot = T(0.5);                // kdot at rho = 1
+            return var(v1);                                  // xy' = xx' = xx/2
+        }
+        return relu_elem<T, NTK>(c, v1, *vy, exact, kdot);
+    }
+    __device__ __forceinline__ T var(T v) const { return v / T(2); }
+};
+
+// erf: one evaluation mode, kdot from the square root K' already paid for
+template <typename T>
+struct ErfMap {
+    template <bool NTK>
+    __device__ __forceinline__ T pair(T c, const T* vx, const T* vy, bool self, T& kdot) const {
+        const T v1 = *vx;
+        if (self) return erf_var(v1, kdot);                  // xy' = xx'
+        const T v2 = *vy;
+        T d = T(1) + T(2) * (v1 + v2) + T(4) * (v1 * v2 - c * c);
+        d = d < T(1) ? T(1) : d;                             // NaN kept
+        const T s = sqrt_t(d);
+        kdot = KErf<T>::four_over_pi / s;                    // dead code without NTK
+        return KErf<T>::two_over_pi * atan_t((T(2) * c) / s);
+    }
+    __device__ __forceinline__ T var(T v) const { return erf_var(v); }
+};
+
+// GELU (gelu_math.h)
+template <typename T>
+struct GeluMap {
+    template <bool NTK>
+    __device__ __forceinline__ T pair(T c, const T* vx, const T* vy, bool self, T& kdot) const {
+        return gelu_pair(c, vx, vy, self, kdot);             // kdot: dead code without NTK
+    }
+    __device__ __forceinline__ T var(T v) const { return gelu_var(v); }
+};
+
+// The two-slope ReLU φ(x) = a·min(x, 0) + b·max(x, 0) is affine in the ReLU's
+// two maps: with the host's s = (a − b)², m = a·b, h = (a² + b²)/2,
+//   K' = fma(s, R, m·c)      κ̇ = fma(s, k, m)      v' = h·v
+// and h·v, κ̇ = h where the ReLU overrides, so (a, b) = (0, 1) gives the ReLU's bits.
+template <typename T>
+struct ABReluMap {
+    T s, m, h;
+    int exact;
+    template <bool NTK>
+    __device__ __forceinline__ T pair(T c, const T* vx, const T* vy, bool self, T& kdot) const {
+        const T v1 = *vx;
+        if (self) {
+            if constexpr (NTK) kdot = h;
+            return var(v1);
+        }
+        T k;
+        const T r = relu_elem<T, NTK>(c, v1, *vy, exact, k);
+        if constexpr (NTK) kdot = fma_t(s, k, m);
+        const T t = m * c;
+        return fma_t(s, r, t);
+    }
+    __device__ __forceinline__ T var(T v) const { return h * v; }
+};
+
+// The post-stage of the conv kernels on position-pair maps (covpool.hip, covntk.hip): the map
+// of run-time `kind` at (c, v1, v2) = (S[p, q], xx_i[p], yy_j[q]).  The override applies where
+// same, i == j and p == q.  The forward conv has no GELU post-stage (cgp_cov_conv_* rejects
+// it), so without NTK every kind but the ReLU is erf.
+template <typename T, bool NTK>
+__device__ __forceinline__ T cov_nonlin(T c, int kind, const T* xx, const T* yy, int i, int j,
+                                        int hw, int p, int q, int same, int exact, T& kdot) {
+    const T* vx = xx + (size_t)i * hw + p;
+    const T* vy = yy + (size_t)j * hw + q;
+    const bool self = same && i == j && p == q;
+    if (kind == CGP_COV_RELU)
+        return ReluMap<T>{exact}.template pair<NTK>(c, vx, vy, self, kdot);
+    if (!NTK || kind == CGP_COV_ERF) return ErfMap<T>{}.template pair<NTK>(c, vx, vy, self, kdot);
+    return GeluMap<T>{}.template pair<NTK>(c, vx, vy, self, kdot);
+}
+
+// ----------------------------------------------------------------------------------
+// the layer path: pair map m = i·n2 + j (or i = j = m with diag) of hw pixels; a workgroup
+// takes mpb whole maps, at most kWalkChunk elements.  theta / out_theta are read with NTK,
+// addend with ADD.
+// ----------------------------------------------------------------------------------
+template <typename T, class F>
+struct PairWalkP {
+    const T* xy;
+    const T* theta;
+    T* out_xy;
+    T* out_theta;
+    const T* addend;
+    const T* xx;
+    const T* yy;       // may be NULL when same && diag: every element is `self`
+    long long nmaps;
+    FastDiv n2, dhw;
+    int hw, same, diag, mpb;
+    F f;
+};
+
+template <typename T, class F, bool NTK, bool ADD>
+__global__ __launch_bounds__(kWalkBlock) void pair_walk_kernel(const PairWalkP<T, F> p) {
+    const long long m0 = (long long)blockIdx.x * p.mpb;
+    const long long rem = p.nmaps - m0;
+    const int mb = rem < p.mpb ? (int)rem : p.mpb;
+    const int n = mb * p.hw;
+    const T* src = p.xy + m0 * p.hw;
+    const T* tsrc = NTK ? p.theta + m0 * p.hw : nullptr;
+    T* dst = p.out_xy + m0 * p.hw;
+    T* tdst = NTK ? p.out_theta + m0 * p.hw : nullptr;
+    const T* add = ADD ? p.addend + m0 * p.hw : nullptr;
+    T v[kWalkE], th[NTK ? kWalkE : 1];
+#pragma unroll
+    for (int k = 0; k < kWalkE; ++k) {
+        const int e = threadIdx.x + k * kWalkBlock;
+        v[k] = e < n ? src[e] : T(0);
+        if constexpr (NTK) th[k] = e < n ? tsrc[e] : T(0);
+    }
+#pragma unroll
+    for (int k = 0; k < kWalkE; ++k) {
+        const int e = threadIdx.x + k * kWalkBlock;
+        if (e < n) {
+            const unsigned ml = fdiv((unsigned)e, p.dhw);
+            const int px = e - (int)ml * p.hw;
+            unsigned i, j;
+            pair_of((unsigned)(m0 + ml), p.n2, p.diag, i, j);
+            const bool self = p.same && (p.diag || i == j);
+            T kd;
+            T r = p.f.template pair<NTK>(v[k], p.xx + (size_t)i * p.hw + px,
+                                         p.yy + (size_t)j * p.hw + px, self, kd);
+            if constexpr (ADD) r = r + add[e];
+            dst[e] = r;
+            if constexpr (NTK) tdst[e] = th[k] * kd;
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------
+// position-pair maps: element -> pixels p = p_row·w + p_col, q = q_row·w + q_col (CovIdx,
+// cov_decode: cgp_common.h); one kWalkChunk-element chunk per workgroup.  ADD: the forward
+// kernel has its addend; the two-stream kernel an addend on either stream, each pointer
+// tested on its own.
+// ----------------------------------------------------------------------------------
+template <typename T, class F>
+struct CovWalkP {
+    const T* in;
+    const T* theta;
+    T* out;
+    T* out_theta;
+    const T* addend;
+    const T* addend_theta;
+    const T* xx;
+    const T* yy;
+    const int* pi;
+    const int* pj;
+    long long total;
+    CovIdx g;
+    int hw, same;
+    F f;
+};
+
+template <typename T, class F, bool NTK, bool ADD>
+__global__ __launch_bounds__(kWalkBlock) void cov_walk_kernel(const CovWalkP<T, F> p) {
+    const long long base = (long long)blockIdx.x * kWalkChunk;
+    const long long rem = p.total - base;
+    const int n = rem < kWalkChunk ? (int)rem : kWalkChunk;
+    const long long m0 = base / p.g.dn.d;
+    const unsigned r0 = (unsigned)(base - m0 * p.g.dn.d);
+    const T* src = p.in + base;
+    const T* tsrc = NTK ? p.theta + base : nullptr;
+    T* dst = p.out + base;
+    T* tdst = NTK ? p.out_theta + base : nullptr;
+    T v[kWalkE], th[NTK ? kWalkE : 1];
+#pragma unroll
+    for (int k = 0; k < kWalkE; ++k) {
+        const int e = threadIdx.x + k * kWalkBlock;
+        v[k] = e < n ? src[e] : T(0);
+        if constexpr (NTK) th[k] = e < n ? tsrc[e] : T(0);
+    }
+#pragma unroll
+    for (int k = 0; k < kWalkE; ++k) {
+        const int e = threadIdx.x + k * kWalkBlock;
+        if (e < n) {
+            const unsigned rt = r0 + (unsigned)e;
+            const unsigned mm = fdiv(rt, p.g.dn);
+            const long long m = m0 + mm;
+            int px, qx;
+            cov_decode(p.g, rt - mm * p.g.dn.d, px, qx);
+            const int i = p.pi[m], j = p.pj[m];
+            // the override applies where both arguments are one pre-activation
+            const bool self = p.same && i == j && px == qx;
+            T kd;
+            T r = p.f.template pair<NTK>(v[k], p.xx + (size_t)i * p.hw + px,
+                                         p.yy + (size_t)j * p.hw + qx, self, kd);
+            if constexpr (ADD) {
+                if (!NTK || p.addend) r = r + p.addend[base + e];
+            }
+            dst[e] = r;
+            if constexpr (NTK) {
+                T t = th[k] * kd;
+                if constexpr (ADD) {
+                    if (p.addend_theta) t = t + p.addend_theta[base + e];
+                }
+                tdst[e] = t;
+            }
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------
+// the per-image variances (kernels.py:154-164): xo = var(xx), yo = var(same ? xx : yy)
+// ----------------------------------------------------------------------------------
+template <typename T, class F>
+struct VarWalkP {
+    const T* xx;
+    const T* yy;
+    T* xo;
+    T* yo;
+    long long n_xx, n_yy;
+    int same;
+    F f;
+};
+
+template <typename T, class F>
+__global__ __launch_bounds__(kWalkBlock) void var_walk_kernel(const VarWalkP<T, F> p) {
+    const T* __restrict__ xx = p.xx;
+    const T* __restrict__ yy = p.yy;
+    const long long stride = (long long)gridDim.x * kWalkBlock;
+    for (long long e = (long long)blockIdx.x * kWalkBlock + threadIdx.x; e < p.n_xx + p.n_yy;
+         e += stride) {
+        if (e < p.n_xx) {
+            p.xo[e] = p.f.var(xx[e]);
+        } else {
+            const long long f = e - p.n_xx;
+            p.yo[f] = p.f.var(p.same ? xx[f] : yy[f]);
+        }
+    }
+}
+
+}  // namespace cgp
