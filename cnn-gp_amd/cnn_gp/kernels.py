@@ -49,6 +49,30 @@ def _check_1x1(plan):
                            " per pair, not 1x1: add a final Conv2d covering the map")
 
 
+def _variances(plan, x, y, same, stream, need=None, what="cgp_moments_var"):
+    """The per-image variances of the inputs (kernels.py:48-49), then the layer path's
+    variance pipeline: the maps of plan.need_var, or of ``need``.  ``what`` names the first
+    call in an error message (a run on position-pair maps adds the dtype)."""
+    n1, c, h, w = x.shape
+    n2 = y.shape[0]
+    var0 = torch.empty((n1 + n2, h, w), dtype=x.dtype, device=x.device)
+    N.check(getattr(N.load(), f"cgp_moments_var_{Plan._sfx(x.dtype)}")(
+        N.ptr(x), N.ptr(y), n1, n2, c, h * w, N.ptr(var0[:n1]), N.ptr(var0[n1:]), stream),
+        what)
+    return plan.run_variances(var0[:n1], var0[n1:], n1, n2, same, stream, need=need)
+
+
+def _moments_xy(x, y, diag, stream):
+    """The input moments' pair maps (kernels.py:44-47): [N1·N2, H, W], or [N1, H, W] of the
+    pairs (i, i) with diag."""
+    n1, c, h, w = x.shape
+    n2 = y.shape[0]
+    xy0 = torch.empty((n1 if diag else n1 * n2, h, w), dtype=x.dtype, device=x.device)
+    N.check(getattr(N.load(), f"cgp_moments_xy_{Plan._sfx(x.dtype)}")(
+        N.ptr(x), N.ptr(y), n1, n2, c, h * w, int(diag), N.ptr(xy0), stream), "cgp_moments_xy")
+    return xy0
+
+
 def _pair_results(r, pi, pj, n1, n2, same, diag):
     """The [npairs] results of a run on position-pair maps as [n1] (diag), [n1, n2], or, from
     the pairs i <= j of a same tile, [n1, n1] mirrored: symmetric bit for bit."""
@@ -282,18 +306,24 @@ class NNGPKernel(nn.Module):
                                "(there is no CPU path)")
         return torch.device("cuda", torch.cuda.current_device())
 
-    def forward(self, x, y=None, same=None, diag=False):
-        """[N1,C,H,W] × [N2,C,H,W] -> kernel [N1,N2] (or [N1] when diag)."""
-        y, same, diag, empty = self._prologue(x, y, same, diag)
-        if empty is not None:
-            return empty
+    def _on_compute_device(self, x, y, run):
+        """run(x, y, stream) with the images on the compute device and that device current;
+        the tensors it returns, moved back to where x lives."""
         out_device = x.device
         dev = self._compute_device(x)
         with torch.cuda.device(dev):
             xd = _to_device(x, dev)
             yd = xd if y is x else _to_device(y.to(x.dtype), dev)
-            r = self._run(xd, yd, same, diag, _stream_handle(dev))
-        return r.to(out_device) if out_device != dev else r
+            outs = run(xd, yd, _stream_handle(dev))
+        return [o.to(out_device) for o in outs] if out_device != dev else outs
+
+    def forward(self, x, y=None, same=None, diag=False):
+        """[N1,C,H,W] × [N2,C,H,W] -> kernel [N1,N2] (or [N1] when diag)."""
+        y, same, diag, empty = self._prologue(x, y, same, diag)
+        if empty is not None:
+            return empty
+        return self._on_compute_device(
+            x, y, lambda xd, yd, stream: [self._run(xd, yd, same, diag, stream)])[0]
 
     def ntk(self, x, y=None, same=None, diag=False, return_nngp=False):
         """The neural tangent kernel Θ of the model, [N1, N2] (or [N1] when diag); with
@@ -339,14 +369,8 @@ class NNGPKernel(nn.Module):
                                       AVGPOOL_RULE_NTK if "avgpool" in kinds else POOL_RULE_NTK)
         if empty is not None:
             return (empty, empty.clone()) if return_nngp else empty
-        out_device = x.device
-        dev = self._compute_device(x)
-        with torch.cuda.device(dev):
-            xd = _to_device(x, dev)
-            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
-            k, th = self._run_ntk(xd, yd, same, diag, _stream_handle(dev))
-        if out_device != dev:
-            k, th = k.to(out_device), th.to(out_device)
+        k, th = self._on_compute_device(
+            x, y, lambda xd, yd, stream: self._run_ntk(xd, yd, same, diag, stream))
         return (k, th) if return_nngp else th
 
     def _run_ntk(self, x, y, same, diag, stream):
@@ -360,21 +384,10 @@ class NNGPKernel(nn.Module):
             # whole-network kernel's fp64 ReLU and cgp_relu_* differ by an ulp on some pixels)
             k = self._run(x, y, same, diag, stream)
             return k, torch.zeros_like(k)
-        sfx = Plan._sfx(x.dtype)
-        lib = N.load()
-        # per-image variances of the inputs (kernels.py:48-49), then of every ReLU's source
-        var0 = torch.empty((n1 + n2, h, w), dtype=x.dtype, device=x.device)
-        N.check(getattr(lib, f"cgp_moments_var_{sfx}")(N.ptr(x), N.ptr(y), n1, n2, c, h * w,
-                                                        N.ptr(var0[:n1]), N.ptr(var0[n1:]),
-                                                        stream), "cgp_moments_var")
-        var = plan.run_variances(var0[:n1], var0[n1:], n1, n2, same, stream,
-                                 need=plan.ntk_need_var())
-        nmaps = n1 if diag else n1 * n2
-        xy0 = torch.empty((nmaps, h, w), dtype=x.dtype, device=x.device)
-        N.check(getattr(lib, f"cgp_moments_xy_{sfx}")(N.ptr(x), N.ptr(y), n1, n2, c, h * w,
-                                                       int(diag), N.ptr(xy0), stream),
-                "cgp_moments_xy")
-        k, th = plan.run_pairs_ntk(xy0, var, n1, n2, same, diag, stream)
+        var = _variances(plan, x, y, same, stream, plan.ntk_need_var())
+        k, th = plan.run_layer_steps(plan.layer_list(ntk=True), x, y,
+                                     _moments_xy(x, y, diag, stream), var, n1, n2, same, diag,
+                                     stream)
         if th is None:
             th = torch.zeros_like(k)
         elif th is k:
@@ -386,8 +399,6 @@ class NNGPKernel(nn.Module):
         n1, c, h, w = x.shape
         n2 = y.shape[0]
         plan = self._plan(h, w)
-        sfx = Plan._sfx(x.dtype)
-        lib = N.load()
         if plan.pool is not None:     # GlobalAvgPool, AvgPool2d, CorrelatedConv2d: DESIGN §3.3-5
             _check_1x1(plan)
             r, _, pi, pj = self._run_cov(plan, plan.pool, x, y, same, diag, stream)
@@ -417,39 +428,17 @@ class NNGPKernel(nn.Module):
                 var, qvar = fused
                 return net.run(x, y, var, n1, n2, same, stream, plan.flags,
                                qvar=qvar or None)
-        # per-image variances of the inputs (kernels.py:48-49)
-        var0 = torch.empty((n1 + n2, h, w), dtype=x.dtype, device=x.device)
-        N.check(getattr(lib, f"cgp_moments_var_{sfx}")(N.ptr(x), N.ptr(y), n1, n2, c, h * w,
-                                                        N.ptr(var0[:n1]), N.ptr(var0[n1:]),
-                                                        stream), "cgp_moments_var")
         if net is not None:                                      # whole-network kernel
-            var = plan.run_variances(var0[:n1], var0[n1:], n1, n2, same, stream,
-                                     need=net.need_var)
+            var = _variances(plan, x, y, same, stream, net.need_var)
             return net.run(x, y, var, n1, n2, same, stream, plan.flags)
-        var = plan.run_variances(var0[:n1], var0[n1:], n1, n2, same, stream)
-        xy0 = None
-        if not plan.moments_fused:
-            nmaps = n1 if diag else n1 * n2
-            xy0 = torch.empty((nmaps, h, w), dtype=x.dtype, device=x.device)
-            N.check(getattr(lib, f"cgp_moments_xy_{sfx}")(N.ptr(x), N.ptr(y), n1, n2, c, h * w,
-                                                           int(diag), N.ptr(xy0), stream),
-                    "cgp_moments_xy")
-        out = plan.run_pairs(x, y, xy0, var, n1, n2, same, diag, stream)
+        var = _variances(plan, x, y, same, stream)
+        xy0 = None if plan.moments_fused else _moments_xy(x, y, diag, stream)
+        out, _ = plan.run_layer_steps(plan.layer_list(), x, y, xy0, var, n1, n2, same, diag,
+                                      stream)
         _check_1x1(plan)
         return out.view(n1) if diag else out.view(n1, n2)
 
     # ---- position-pair maps: GlobalAvgPool, AvgPool2d, CorrelatedConv2d and their NTK ----
-    def _on_compute_device(self, x, y, run):
-        """run(x, y, stream) with the images on the compute device and that device current;
-        the tensors it returns, moved back to where x lives."""
-        out_device = x.device
-        dev = self._compute_device(x)
-        with torch.cuda.device(dev):
-            xd = _to_device(x, dev)
-            yd = xd if y is x else _to_device(y.to(x.dtype), dev)
-            outs = run(xd, yd, _stream_handle(dev))
-        return [o.to(out_device) for o in outs] if out_device != dev else outs
-
     def _run_cov(self, plan, cs, x, y, same, diag, stream):
         """Runs the launch list ``cs`` (program.pool_steps or pool_ntk_steps) on the pairs of a
         tile: all of them, the pairs i <= j of a same tile, or (i, i) for diag.  Returns
@@ -466,9 +455,7 @@ class NNGPKernel(nn.Module):
     def _pool_pairs(self, plan, ps, x, y, same, diag, stream):
         """The pair lists of a tile (int64 index tensors), the variance maps ``ps`` reads
         and the workspace bound: what a run on position-pair maps starts from."""
-        n1, c, h, w = x.shape
-        n2 = y.shape[0]
-        dev = x.device
+        n1, n2, dev = x.shape[0], y.shape[0], x.device
         if diag:
             pi = pj = torch.arange(n1, device=dev)
         elif same:
@@ -479,13 +466,9 @@ class NNGPKernel(nn.Module):
         var = {}
         ws = getattr(self, "_cgp_pool_ws", None)
         if ps.need_var - ps.self_var:
-            # per-image variances of the inputs (kernels.py:48-49), then of every value a
-            # nonlinearity reads: the layer path's own pipeline
-            var0 = torch.empty((n1 + n2, h, w), dtype=x.dtype, device=dev)
-            N.call(f"cgp_moments_var_{Plan._sfx(x.dtype)}", N.ptr(x), N.ptr(y), n1, n2, c,
-                   h * w, N.ptr(var0[:n1]), N.ptr(var0[n1:]), stream)
-            var = plan.run_variances(var0[:n1], var0[n1:], n1, n2, same, stream,
-                                     need=set(ps.need_var - ps.self_var))
+            # the layer path's own pipeline
+            var = _variances(plan, x, y, same, stream, set(ps.need_var - ps.self_var),
+                             "cgp_moments_var_" + Plan._sfx(x.dtype))
         if ps.self_var:
             # downstream of an AvgPool2d the variances are the p = q diagonals of the images'
             # self position-pair maps: the same launches over the pairs (i, i)

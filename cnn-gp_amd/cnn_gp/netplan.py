@@ -1,6 +1,6 @@
 """Lowering of a compiled program to the whole-network pair kernel (cgp_net_*).
 
-The layer-by-layer pair pipeline (program.Plan.run_pairs) writes every intermediate
+The layer-by-layer pair pipeline (program.Plan.run_layer_steps) writes every intermediate
 [N1·N2, H, W] map to HBM.  ``NetPlan`` instead lowers the SAME SSA program
 (program.compile_program) to a list of ``cgp_net_op`` over LDS slots, executed per pair
 by one workgroup (csrc/netfuse.hip).  Semantics per op, with the reference lines:

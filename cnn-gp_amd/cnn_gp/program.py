@@ -31,6 +31,11 @@ and then split into two device pipelines:
 
 Fusion changes no arithmetic: each fused stage performs exactly the operations of the
 op it replaces (a + b == b + a in IEEE, so folding a Sum into either branch is exact).
+
+Every run on pair maps is lowered once per plan to a list of Step records, each with the
+buffers to drop after it: layer_steps (the fused forward run) and ntk_steps (K and Θ through
+the unfused program) run in Plan.run_layer_steps; pool_steps and pool_ntk_steps, on
+position-pair maps, in Plan.run_cov_steps.
 """
 from __future__ import annotations
 
@@ -186,26 +191,15 @@ def _emit(prog: Program, mod, v: int) -> int:
         prog.ops.append(Op("conv", out, src=v, geom=conv_geometry(mod), shape_in=(h, w),
                            shape_out=(ho, wo)))
         return out
-    if isinstance(mod, K.ReLU):
+    # one table from module class to elementwise kind (LeakyReLU is an ABReLU)
+    kind = next((k for cls, k in ((K.ReLU, "relu"), (K.Erf, "erf"), (K.Gelu, "gelu"),
+                                  (K.ABReLU, "abrelu")) if isinstance(mod, cls)), None)
+    if kind is not None:
         out = prog.new_value(prog.shapes[v])
-        prog.ops.append(Op("relu", out, src=v, shape_in=prog.shapes[v],
-                           shape_out=prog.shapes[v]))
-        return out
-    if isinstance(mod, K.Erf):
-        out = prog.new_value(prog.shapes[v])
-        prog.ops.append(Op("erf", out, src=v, shape_in=prog.shapes[v],
-                           shape_out=prog.shapes[v]))
-        return out
-    if isinstance(mod, K.Gelu):
-        out = prog.new_value(prog.shapes[v])
-        prog.ops.append(Op("gelu", out, src=v, shape_in=prog.shapes[v],
-                           shape_out=prog.shapes[v]))
-        return out
-    if isinstance(mod, K.ABReLU):
-        out = prog.new_value(prog.shapes[v])
-        prog.ops.append(Op("abrelu", out, src=v, shape_in=prog.shapes[v],
-                           shape_out=prog.shapes[v], slopes=(float(mod.a), float(mod.b)),
-                           smh=mod.constants()))
+        consts = dict(slopes=(float(mod.a), float(mod.b)), smh=mod.constants()) \
+            if kind == "abrelu" else {}
+        prog.ops.append(Op(kind, out, src=v, shape_in=prog.shapes[v], shape_out=prog.shapes[v],
+                           **consts))
         return out
     if isinstance(mod, K.GlobalAvgPool):
         out = prog.new_value((1, 1))
@@ -387,39 +381,144 @@ def needed_variances(ops) -> set:
 # the neural tangent kernel: a second pair map Θ beside K
 # ------------------------------------------------------------------------------------
 @dataclasses.dataclass
-class NtkStep:
-    """One launch of the NTK run.  Buffers are named ("K", value) / ("T", value): the K
-    and Θ maps of an SSA value.
+class Step:
+    """One launch of a lowered run: of the layer path's lists (layer_steps, ntk_steps: pair
+    maps, Plan.run_layer_steps) or of a list on position-pair maps (pool_steps,
+    pool_ntk_steps, Plan.run_cov_steps).  pool_steps names a buffer by the SSA value it holds;
+    the other three by ("K", v) / ("T", v), the K and Θ maps of value v, with v = ("pre", d)
+    in pool_ntk_steps for the conv output that a fused addend replaced in the forward program.
+    ``free``: the buffers nothing reads after this launch (_schedule).
 
+    The layer path's lists hold
     fn "conv":     dst = A(src)·weight + bias [+ addend]     cgp_conv_* (op.geom; ``bias``
-                   replaces the geometry's: 0 on the Θ stream)
-    fn "relu":     dst = relu(src), variances of value ``var``           cgp_relu_*
+                   replaces the geometry's: 0 on the Θ stream).  In layer_steps op is the FUSED
+                   op, with its pre / post stages and their variances, and src is None where
+                   the stage is the input moments (the conv reads the images)
+    fn "relu":     dst = relu(src) [+ addend], variances of value ``var``  cgp_relu_*
     fn "relu_ntk": dst, dst_theta = relu(src), theta·κ̇                   cgp_relu_ntk_*
-    fn "erf":      dst = erf(src), variances of value ``var``            cgp_erf_* (theta NULL)
+    fn "erf":      dst = erf(src) [+ addend], variances of ``var``       cgp_erf_* (theta NULL)
     fn "erf_ntk":  dst, dst_theta = erf(src), theta·κ̇                    cgp_erf_*
-    fn "gelu":     dst = gelu(src), variances of value ``var``           cgp_gelu_* (theta NULL)
+    fn "gelu":     dst = gelu(src) [+ addend], variances of ``var``      cgp_gelu_* (theta NULL)
     fn "gelu_ntk": dst, dst_theta = gelu(src), theta·κ̇                   cgp_gelu_*
-    fn "abrelu":   dst = abrelu(src; op.smh), variances of ``var``       cgp_abrelu_* (theta NULL)
+    fn "abrelu":   dst = abrelu(src; op.smh) [+ addend], variances of ``var``
+                                                                         cgp_abrelu_* (theta NULL)
     fn "abrelu_ntk": dst, dst_theta = abrelu(src), theta·κ̇               cgp_abrelu_*
     fn "axpby":    dst = Σ coef·buffer over ``terms`` (coef None: 1)     cgp_axpby_*
-    """
+
+    Either list on position-pair maps may hold
+    fn "moments": dst = mean_c x[c, p]·y[c, q]                          cgp_cov_moments_*
+    fn "conv":    dst = A(src)·weight + bias [→ ReLU, variances of value ``var``]
+                  [+ addend]; ``bias`` replaces the geometry's (0 on the Θ stream)
+                                                                         cgp_cov_conv_*
+    fn "nonlin":  dst = relu / erf (``post``) of src, variances of value ``var``
+                  [+ addend]                                             cgp_cov_nonlin_*
+    fn "gelu":    dst = gelu of src, variances of value ``var`` [+ addend]
+                                                                         cgp_gelu_cov_*
+    fn "abrelu":  dst = abrelu of src (op.smh), variances of value ``var`` [+ addend]
+                                                                         cgp_abrelu_cov_*
+    fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
+    fn "avgpool": dst = mean of src over the windows of p and of q (op.geom)
+                                                                         cgp_covmap_avgpool_*
+    fn "corrconv": dst = the correlated-weight conv of src (op.geom, ``bias``)
+                                                                         cgp_corrconv_*
+    fn "axpby":   dst = Σ coef·buffer over ``terms`` (coef None: 1)      cgp_axpby_*
+
+    and the two-stream list also
+    fn "conv_ntk":   dst, dst_theta = the two-stream conv of (src, theta), theta None for
+                     Θ = 0, [→ nonlinearity ``post``] [+ addend, + addend_theta]
+                                                                          cgp_covntk_conv_*
+    fn "nonlin_ntk": dst, dst_theta = ``post`` of src [+ addend], theta·κ̇ [+ addend_theta]
+                                                                          cgp_covntk_nonlin_*
+    fn "abrelu_ntk": dst, dst_theta = abrelu of src [+ addend], theta·κ̇ [+ addend_theta]
+                                                                          cgp_abrelu_cov_*
+    fn "accum":      dst = dst + src, in place                            cgp_axpby_*"""
     fn: str
-    dst: tuple
-    src: Optional[tuple] = None
+    dst: object
+    src: Optional[object] = None
     op: Optional[Op] = None
-    bias: float = 0.0
-    addend: Optional[tuple] = None
+    post: int = N.CGP_COV_NONE
     var: Optional[int] = None
+    addend: Optional[object] = None
+    bias: Optional[float] = None
     theta: Optional[tuple] = None
     dst_theta: Optional[tuple] = None
+    addend_theta: Optional[tuple] = None
     terms: list = dataclasses.field(default_factory=list)
+    free: list = dataclasses.field(default_factory=list)
 
     def reads(self):
-        r = [b for b in (self.src, self.addend, self.theta) if b is not None]
+        r = [b for b in (self.src, self.addend, self.theta, self.addend_theta)
+             if b is not None]
+        if self.fn == "accum":
+            r.append(self.dst)
         return r + [b for _, b in self.terms]
 
     def writes(self):
         return [b for b in (self.dst, self.dst_theta) if b is not None]
+
+
+def _schedule(steps, elems, keep, key=None, given=()):
+    """Sets every step's ``free`` -- the live buffers no later step reads, those of ``keep``
+    never, sorted by ``key`` -- and returns (peak, largest): the elements, by ``elems(buffer)``,
+    live at the fullest launch and of the largest buffer.  ``given``: the buffers that exist
+    before the first launch."""
+    last = {}
+    for idx, st in enumerate(steps):
+        for b in st.reads():
+            last[b] = idx
+    last.update((b, len(steps)) for b in keep)
+    live = set(given)
+    peak = largest = 0
+    for idx, st in enumerate(steps):
+        live.update(st.writes())
+        peak = max(peak, sum(elems(b) for b in live))
+        largest = max([largest] + [elems(b) for b in st.writes()])
+        st.free = sorted((b for b in live if last.get(b, -1) <= idx), key=key)
+        live.difference_update(st.free)
+    return peak, largest
+
+
+def _theta_sum(terms, theta, d):
+    """The Sum / Mixture rule for Θ of value ``d`` = Σ coef·value over ``terms``, with
+    theta[value] the buffer that holds a term's Θ (None: zero).  Zero terms are skipped and a
+    single term of weight 1 passes its buffer on.  Returns (the buffer of Θ(d) or None, the
+    terms of the cgp_axpby_* launch that writes it: none where no launch is needed)."""
+    live = [(c, theta[t]) for c, t in terms if theta[t] is not None]
+    if not live:
+        return None, []
+    if len(live) == 1 and live[0][0] is None:
+        return live[0][1], []
+    return ("T", d), live
+
+
+def _layer_schedule(prog, steps, keep, given):
+    """_schedule for a layer-path list: a buffer ("K", v) / ("T", v) is ho·wo elements per
+    map."""
+    _schedule(steps, lambda b: prog.shapes[b[1]][0] * prog.shapes[b[1]][1], keep, given=given)
+
+
+def layer_steps(prog: Program, pair_ops, v0: int, vf: int):
+    """The forward run of the layer path: the fused op list ``pair_ops`` (fuse) in step form,
+    one step per op, in order.  Returns (steps, k, None) as ntk_steps does, k = ("K", vf).
+    The input moments' maps ("K", v0) are given to the run unless a conv computes them as its
+    pre-stage."""
+    K = lambda v: None if v is None else ("K", v)                               # noqa: E731
+    steps = []
+    for op in pair_ops:
+        if op.kind == "conv":
+            src = None if op.pre == N.CGP_PRE_MOMENTS else K(op.src)
+            steps.append(Step("conv", K(op.dst), src=src, op=op, bias=op.geom.bias,
+                              addend=K(op.addend)))
+        elif op.kind in NONLIN_KINDS:
+            steps.append(Step(op.kind, K(op.dst), src=K(op.src), op=op, var=op.src,
+                              addend=K(op.addend)))
+        elif op.kind == "add":
+            steps.append(Step("axpby", K(op.dst), op=op, terms=[(c, K(t)) for c, t in op.terms]))
+        else:
+            raise AssertionError(op.kind)
+    fused = any(op.pre == N.CGP_PRE_MOMENTS for op in pair_ops)
+    _layer_schedule(prog, steps, [K(vf)], [] if fused else [K(v0)])
+    return steps, K(vf), None
 
 
 def ntk_steps(prog: Program, v0: int, vf: int):
@@ -445,36 +544,28 @@ def ntk_steps(prog: Program, v0: int, vf: int):
     steps = []
     theta = {v0: None}
     for op in prog.ops:
-        d = op.dst
+        d, th = op.dst, theta.get(op.src)
         if op.kind == "conv":
-            steps.append(NtkStep("conv", ("K", d), src=("K", op.src), op=op, bias=op.geom.bias))
-            if theta[op.src] is None:
-                theta[d] = ("K", d)
-            else:
-                steps.append(NtkStep("conv", ("T", d), src=theta[op.src], op=op, bias=0.0,
-                                     addend=("K", d)))
+            steps.append(Step("conv", ("K", d), src=("K", op.src), op=op, bias=op.geom.bias))
+            theta[d] = ("K", d)
+            if th is not None:
+                steps.append(Step("conv", ("T", d), src=th, op=op, bias=0.0, addend=("K", d)))
                 theta[d] = ("T", d)
         elif op.kind in NONLIN_KINDS:
-            if theta[op.src] is None:
-                steps.append(NtkStep(op.kind, ("K", d), src=("K", op.src), op=op, var=op.src))
-                theta[d] = None
-            else:
-                steps.append(NtkStep(op.kind + "_ntk", ("K", d), src=("K", op.src), op=op,
-                                     var=op.src, theta=theta[op.src], dst_theta=("T", d)))
-                theta[d] = ("T", d)
+            theta[d] = None if th is None else ("T", d)
+            steps.append(Step(op.kind if th is None else op.kind + "_ntk", ("K", d),
+                              src=("K", op.src), op=op, var=op.src, theta=th,
+                              dst_theta=theta[d]))
         elif op.kind == "add":
-            steps.append(NtkStep("axpby", ("K", d), op=op,
-                                 terms=[(c, ("K", t)) for c, t in op.terms]))
-            live = [(c, theta[t]) for c, t in op.terms if theta[t] is not None]
-            if not live:
-                theta[d] = None
-            elif len(live) == 1 and live[0][0] is None:
-                theta[d] = live[0][1]
-            else:
-                steps.append(NtkStep("axpby", ("T", d), op=op, terms=live))
-                theta[d] = ("T", d)
+            steps.append(Step("axpby", ("K", d), op=op,
+                              terms=[(c, ("K", t)) for c, t in op.terms]))
+            theta[d], live = _theta_sum(op.terms, theta, d)
+            if live:
+                steps.append(Step("axpby", theta[d], op=op, terms=live))
         else:
             raise AssertionError(op.kind)
+    final = [b for b in (("K", vf), theta[vf]) if b is not None]
+    _layer_schedule(prog, steps, final, [("K", v0)])
     return steps, ("K", vf), theta[vf]
 
 
@@ -501,65 +592,6 @@ ABRELU_RULE_GLOBAL = ("an ABReLU / LeakyReLU downstream of a GlobalAvgPool is no
                       "it would need the pooled self-covariances of each image (DESIGN §8)")
 CORRCONV_RULE_NTK = ("ntk: the neural tangent kernel of a model with a CorrelatedConv2d is not "
                      "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
-
-
-@dataclasses.dataclass
-class CovStep:
-    """One launch of a run on position-pair maps.  pool_steps names a buffer by the SSA value
-    it holds; pool_ntk_steps by ("K", v) / ("T", v), the K and Θ maps of value v, as in
-    ntk_steps, with v = ("pre", d) for the conv output that a fused addend replaced in the
-    forward program.  Either list may hold
-
-    fn "moments": dst = mean_c x[c, p]·y[c, q]                          cgp_cov_moments_*
-    fn "conv":    dst = A(src)·weight + bias [→ ReLU, variances of value ``var``]
-                  [+ addend]; ``bias`` replaces the geometry's (0 on the Θ stream)
-                                                                         cgp_cov_conv_*
-    fn "nonlin":  dst = relu / erf (``post``) of src, variances of value ``var``
-                  [+ addend]                                             cgp_cov_nonlin_*
-    fn "gelu":    dst = gelu of src, variances of value ``var`` [+ addend]
-                                                                         cgp_gelu_cov_*
-    fn "abrelu":  dst = abrelu of src (op.smh), variances of value ``var`` [+ addend]
-                                                                         cgp_abrelu_cov_*
-    fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
-    fn "avgpool": dst = mean of src over the windows of p and of q (op.geom)
-                                                                         cgp_covmap_avgpool_*
-    fn "corrconv": dst = the correlated-weight conv of src (op.geom, ``bias``)
-                                                                         cgp_corrconv_*
-    fn "axpby":   dst = Σ coef·buffer over ``terms`` (coef None: 1)      cgp_axpby_*
-
-    and the two-stream list also
-    fn "conv_ntk":   dst, dst_theta = the two-stream conv of (src, theta), theta None for
-                     Θ = 0, [→ nonlinearity ``post``] [+ addend, + addend_theta]
-                                                                          cgp_covntk_conv_*
-    fn "nonlin_ntk": dst, dst_theta = ``post`` of src [+ addend], theta·κ̇ [+ addend_theta]
-                                                                          cgp_covntk_nonlin_*
-    fn "abrelu_ntk": dst, dst_theta = abrelu of src [+ addend], theta·κ̇ [+ addend_theta]
-                                                                          cgp_abrelu_cov_*
-    fn "accum":      dst = dst + src, in place                            cgp_axpby_*
-    ``free``: the buffers nothing reads after this launch."""
-    fn: str
-    dst: object
-    src: Optional[object] = None
-    op: Optional[Op] = None
-    post: int = N.CGP_COV_NONE
-    var: Optional[int] = None
-    addend: Optional[object] = None
-    bias: Optional[float] = None
-    theta: Optional[tuple] = None
-    dst_theta: Optional[tuple] = None
-    addend_theta: Optional[tuple] = None
-    terms: list = dataclasses.field(default_factory=list)
-    free: list = dataclasses.field(default_factory=list)
-
-    def reads(self):
-        r = [b for b in (self.src, self.addend, self.theta, self.addend_theta)
-             if b is not None]
-        if self.fn == "accum":
-            r.append(self.dst)
-        return r + [b for _, b in self.terms]
-
-    def writes(self):
-        return [b for b in (self.dst, self.dst_theta) if b is not None]
 
 
 @dataclasses.dataclass
@@ -595,23 +627,6 @@ class CovSteps:
     def elems(self, b) -> int:
         h, w = self.shapes[b]
         return (h * w) ** 2 if b in self.maps else 1
-
-
-def _schedule(cs: CovSteps, keep, key=None):
-    """Sets every step's ``free`` -- the live buffers no later step reads, those of ``keep``
-    never, sorted by ``key`` -- and cs.peak and cs.largest."""
-    cs.largest = max(cs.elems(b) for b in cs.shapes)
-    last = {}
-    for idx, st in enumerate(cs.steps):
-        for b in st.reads():
-            last[b] = idx
-    last.update((b, len(cs.steps)) for b in keep)
-    live = set()
-    for idx, st in enumerate(cs.steps):
-        live.update(st.writes())
-        cs.peak = max(cs.peak, sum(cs.elems(b) for b in live))
-        st.free = sorted((b for b in live if last.get(b, -1) <= idx), key=key)
-        live.difference_update(st.free)
 
 
 # op kind -> the rule it breaks downstream of a GlobalAvgPool (its result is not pooled)
@@ -667,31 +682,31 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
     if not body and not pooled[vf]:
         raise NotImplementedError(POOL_RULE_ONE)
 
-    steps = [CovStep("moments", v0)]
+    steps = [Step("moments", v0)]
     for op in fuse(prog, v0, vf, True, pre_relu=False, fold_moments=False):
         if op.kind == "conv" and op.post == N.CGP_POST_RELU and avgpooled[op.post_var]:
-            steps.append(CovStep("conv", op.post_var, src=op.src, op=op, bias=op.geom.bias))
-            steps.append(CovStep("nonlin", op.dst, src=op.post_var, op=op, post=N.CGP_COV_RELU,
+            steps.append(Step("conv", op.post_var, src=op.src, op=op, bias=op.geom.bias))
+            steps.append(Step("nonlin", op.dst, src=op.post_var, op=op, post=N.CGP_COV_RELU,
                                  var=op.post_var, addend=op.addend))
         elif op.kind == "conv":
             relu = op.post == N.CGP_POST_RELU
-            steps.append(CovStep("conv", op.dst, src=op.src, op=op,
+            steps.append(Step("conv", op.dst, src=op.src, op=op,
                                  post=N.CGP_COV_RELU if relu else N.CGP_COV_NONE,
                                  var=op.post_var if relu else None, addend=op.addend,
                                  bias=op.geom.bias))
         elif op.kind in ("relu", "erf"):
-            steps.append(CovStep("nonlin", op.dst, src=op.src, op=op,
+            steps.append(Step("nonlin", op.dst, src=op.src, op=op,
                                  post=N.CGP_COV_RELU if op.kind == "relu" else N.CGP_COV_ERF,
                                  var=op.src, addend=op.addend))
         elif op.kind in ("gelu", "abrelu"):
-            steps.append(CovStep(op.kind, op.dst, src=op.src, op=op, var=op.src,
+            steps.append(Step(op.kind, op.dst, src=op.src, op=op, var=op.src,
                                  addend=op.addend))
         elif op.kind in ("pool", "avgpool"):
-            steps.append(CovStep(op.kind, op.dst, src=op.src, op=op))
+            steps.append(Step(op.kind, op.dst, src=op.src, op=op))
         elif op.kind == "corrconv":
-            steps.append(CovStep("corrconv", op.dst, src=op.src, op=op, bias=op.geom.bias))
+            steps.append(Step("corrconv", op.dst, src=op.src, op=op, bias=op.geom.bias))
         else:
-            steps.append(CovStep("axpby", op.dst, op=op, terms=list(op.terms)))
+            steps.append(Step("axpby", op.dst, op=op, terms=list(op.terms)))
     bufs = [st.dst for st in steps]
     ps = CovSteps(steps, {b: prog.shapes[b] for b in bufs},
                   frozenset(b for b in bufs if not pooled[b]),
@@ -702,7 +717,7 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
     ps.self_var = frozenset(v for v in ps.need_var if avgpooled[v])
     ps.self_last = max((idx for idx, st in enumerate(steps) if st.dst in ps.self_var),
                        default=-1)
-    _schedule(ps, [vf])
+    ps.peak, ps.largest = _schedule(steps, ps.elems, [vf])
     return ps
 
 
@@ -767,50 +782,50 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
         ta = theta.get(st.addend) if st.addend is not None else None
         ka = K(st.addend) if st.addend is not None else None
         if st.fn == "moments":
-            emit(CovStep("moments", K(d)), shape, sc)
+            emit(Step("moments", K(d)), shape, sc)
         elif st.fn == "conv":
             g = op.geom
             plain = st.post == N.CGP_COV_NONE and st.addend is None
             if plain and ts is None:
-                emit(CovStep("conv", K(d), src=K(st.src), op=op, bias=g.bias), shape, sc)
+                emit(Step("conv", K(d), src=K(st.src), op=op, bias=g.bias), shape, sc)
                 theta[d] = K(d)
             elif fused and conv_ntk_fits(g.taps, fwd.shapes[st.src][1],
                                          1 if ts is None else 2, itemsize):
-                emit(CovStep("conv_ntk", K(d), src=K(st.src), op=op, post=st.post,
+                emit(Step("conv_ntk", K(d), src=K(st.src), op=op, post=st.post,
                              var=st.var, addend=ka, bias=g.bias, theta=ts,
                              dst_theta=("T", d), addend_theta=ta), shape, sc)
                 theta[d] = ("T", d)
             else:
                 pre = d if plain else (st.var if st.post != N.CGP_COV_NONE else ("pre", d))
-                emit(CovStep("conv", K(pre), src=K(st.src), op=op, bias=g.bias), shape, sc)
+                emit(Step("conv", K(pre), src=K(st.src), op=op, bias=g.bias), shape, sc)
                 tpre = K(pre)
                 if ts is not None:
                     tpre = ("T", pre)
-                    emit(CovStep("conv", tpre, src=ts, op=op, bias=0.0, addend=K(pre)),
+                    emit(Step("conv", tpre, src=ts, op=op, bias=0.0, addend=K(pre)),
                          shape, sc)
                 if plain:
                     theta[d] = tpre
                 elif st.post != N.CGP_COV_NONE:
-                    emit(CovStep("nonlin_ntk", K(d), src=K(pre), op=op, post=st.post,
+                    emit(Step("nonlin_ntk", K(d), src=K(pre), op=op, post=st.post,
                                  var=st.var, addend=ka, theta=tpre, dst_theta=("T", d),
                                  addend_theta=ta), shape, sc)
                     theta[d] = ("T", d)
                 else:
-                    emit(CovStep("axpby", K(d), op=op, terms=[(None, K(pre)), (None, ka)]),
+                    emit(Step("axpby", K(d), op=op, terms=[(None, K(pre)), (None, ka)]),
                          shape, sc)
                     if ta is None:
                         theta[d] = tpre
                     else:
-                        emit(CovStep("axpby", ("T", d), op=op,
+                        emit(Step("axpby", ("T", d), op=op,
                                      terms=[(None, tpre), (None, ta)]), shape, sc)
                         theta[d] = ("T", d)
         elif st.fn in ("nonlin", "gelu"):
             if ts is None:
-                emit(CovStep(st.fn, K(d), src=K(st.src), op=op, post=st.post, var=st.var,
+                emit(Step(st.fn, K(d), src=K(st.src), op=op, post=st.post, var=st.var,
                              addend=ka), shape, sc)
                 theta[d] = ta
             else:
-                emit(CovStep("nonlin_ntk", K(d), src=K(st.src), op=op,
+                emit(Step("nonlin_ntk", K(d), src=K(st.src), op=op,
                              post=N.CGP_COV_GELU if st.fn == "gelu" else st.post,
                              var=st.var, addend=ka, theta=ts, dst_theta=("T", d),
                              addend_theta=ta), shape, sc)
@@ -818,45 +833,41 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
         elif st.fn == "abrelu":
             # a launch of its own on either run: one entry point, with and without Θ
             if ts is None:
-                emit(CovStep("abrelu", K(d), src=K(st.src), op=op, var=st.var, addend=ka),
+                emit(Step("abrelu", K(d), src=K(st.src), op=op, var=st.var, addend=ka),
                      shape, sc)
                 theta[d] = ta
             else:
-                emit(CovStep("abrelu_ntk", K(d), src=K(st.src), op=op, var=st.var, addend=ka,
+                emit(Step("abrelu_ntk", K(d), src=K(st.src), op=op, var=st.var, addend=ka,
                              theta=ts, dst_theta=("T", d), addend_theta=ta), shape, sc)
                 theta[d] = ("T", d)
         elif st.fn in ("pool", "avgpool"):
-            emit(CovStep(st.fn, K(d), src=K(st.src), op=op), shape, sc)
+            emit(Step(st.fn, K(d), src=K(st.src), op=op), shape, sc)
             theta[d] = None
             if ts is not None:
-                emit(CovStep(st.fn, ("T", d), src=ts, op=op), shape, sc)
+                emit(Step(st.fn, ("T", d), src=ts, op=op), shape, sc)
                 theta[d] = ("T", d)
         elif st.fn == "corrconv":
-            emit(CovStep("corrconv", K(d), src=K(st.src), op=op, bias=op.geom.bias),
+            emit(Step("corrconv", K(d), src=K(st.src), op=op, bias=op.geom.bias),
                  shape, sc)
             theta[d] = K(d)
             if ts is not None:
-                emit(CovStep("corrconv", ("T", d), src=ts, op=op, bias=0.0), shape, sc)
-                emit(CovStep("accum", ("T", d), src=K(d), op=op), shape, sc)
+                emit(Step("corrconv", ("T", d), src=ts, op=op, bias=0.0), shape, sc)
+                emit(Step("accum", ("T", d), src=K(d), op=op), shape, sc)
                 theta[d] = ("T", d)
         elif st.fn == "axpby":
-            emit(CovStep("axpby", K(d), op=op, terms=[(c, K(t)) for c, t in st.terms]),
+            emit(Step("axpby", K(d), op=op, terms=[(c, K(t)) for c, t in st.terms]),
                  shape, sc)
-            live = [(c, theta[t]) for c, t in st.terms if theta[t] is not None]
-            if not live:
-                theta[d] = None
-            elif len(live) == 1 and live[0][0] is None:
-                theta[d] = live[0][1]
-            else:
-                emit(CovStep("axpby", ("T", d), op=op, terms=live), shape, sc)
-                theta[d] = ("T", d)
+            theta[d], live = _theta_sum(st.terms, theta, d)
+            if live:
+                emit(Step("axpby", theta[d], op=op, terms=live), shape, sc)
         else:
             raise AssertionError(st.fn)
 
     ns = CovSteps(steps, shapes, frozenset(b for b in shapes if b not in scalars),
                   frozenset(scalars), K(vf), fwd.need_var, final_theta=theta[vf], forward=fwd,
                   fused=fused)
-    _schedule(ns, [b for b in (ns.final, ns.final_theta) if b is not None], key=repr)
+    ns.peak, ns.largest = _schedule(
+        steps, ns.elems, [b for b in (ns.final, ns.final_theta) if b is not None], key=repr)
     return ns
 
 
@@ -922,8 +933,8 @@ class Plan:
 
     def _nonlin_launch(self, op, sfx, stream, src, out, var, n1, n2, same, diag, addend=None,
                        theta=None, out_theta=None):
-        """Fills the argument record of a layer-path nonlinearity (NONLIN_CALLS) and returns the
-        closure that launches it; with ``theta`` the two-stream form (Θ' = Θ·κ̇)."""
+        """Fills the argument record of a layer-path nonlinearity (NONLIN_CALLS) and launches
+        it; with ``theta`` the two-stream form (Θ' = Θ·κ̇)."""
         name = "relu_ntk" if op.kind == "relu" and theta is not None else op.kind
         cls, out_field, has_flags, has_smh = NONLIN_CALLS[name][:4]
         vx, vy = var
@@ -942,8 +953,38 @@ class Plan:
             r.s, r.m, r.h = op.smh
         if has_flags:
             r.flags = self.flags
-        fn = getattr(N.load(), f"cgp_{name}_{sfx}")
-        return lambda: N.check(fn(r, stream), "cgp_" + name)
+        N.check(getattr(N.load(), f"cgp_{name}_{sfx}")(r, stream), "cgp_" + name)
+
+    @staticmethod
+    def _conv_args(op, src, out, nmaps, n1, n2, same=0, diag=0, flags=0, bias=None, addend=None,
+                   var=None, images=None):
+        """The cgp_conv_* record of conv ``op`` from ``src`` (or, where its pre-stage is the
+        moments, from ``images`` = (x, y)) to ``out``: geometry, shapes, the op's pre / post
+        stages with their variance maps from ``var``, the addend and ``bias`` in place of the
+        geometry's.  A new record is all zeros, so the stages and the addend are written only
+        where the op has them."""
+        g = op.geom
+        a = N.ConvArgs()
+        if op.pre == N.CGP_PRE_MOMENTS:
+            x, y = images
+            a.in_, a.in_y, a.channels, a.pre = x.data_ptr(), y.data_ptr(), x.shape[1], op.pre
+        else:
+            a.in_ = src.data_ptr()
+            if op.pre == N.CGP_PRE_RELU:
+                vx, vy = var[op.pre_var]
+                a.pre_xx, a.pre_yy, a.pre = vx.data_ptr(), vy.data_ptr(), op.pre
+        if op.post == N.CGP_POST_RELU:
+            vx, vy = var[op.post_var]
+            a.post_xx, a.post_yy, a.post = vx.data_ptr(), vy.data_ptr(), op.post
+        a.out = out.data_ptr()
+        if addend is not None:
+            a.addend = addend.data_ptr()
+        a.nmaps, a.n1, a.n2 = nmaps, n1, n2
+        (a.h, a.w), (a.ho, a.wo) = op.shape_in, op.shape_out
+        a.taps, a.offset, a.stride, a.dilation = g.taps, g.offset, g.stride, g.dilation
+        a.same, a.diag, a.flags = same, diag, flags
+        a.weight, a.bias = g.weight, g.bias if bias is None else bias
+        return a
 
     def _last_use(self, ops, extra_final):
         last = {}
@@ -981,20 +1022,13 @@ class Plan:
             if op.kind == "conv":
                 xin, yin = vals[op.src]
                 buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
-                g = op.geom
-                h, w = op.shape_in
                 # xx and yy may live in different allocations: launch per block, or once
                 # over both when they are adjacent (every value after the first is)
                 parts = ((xin, buf[:n1], n1), (yin, buf[n1:], n2))
                 if _adjacent(xin, yin):
                     parts = ((xin, buf, n1 + n2),)
                 for src, dst, n in parts:
-                    a = N.ConvArgs()
-                    a.in_, a.out = N.ptr(src), N.ptr(dst)
-                    a.nmaps, a.n1, a.n2 = n, n, 1
-                    a.h, a.w, a.ho, a.wo = h, w, ho, wo
-                    a.taps, a.offset, a.stride, a.dilation = g.taps, g.offset, g.stride, g.dilation
-                    a.weight, a.bias = g.weight, g.bias
+                    a = self._conv_args(op, src, dst, n, n, 1)
                     N.check(getattr(N.load(), f"cgp_conv_{sfx}")(a, stream), "cgp_conv")
                 out = (buf[:n1], buf[n1:])
             elif op.kind in NONLIN_KINDS:
@@ -1171,142 +1205,59 @@ class Plan:
             qvar[v] = out[base:base + n1 * ho * wo].view(n1, ho, wo)
         return var, qvar
 
-    # -- pair pipeline ------------------------------------------------------------------
-    def run_pairs(self, x, y, xy0, var, n1, n2, same, diag, stream, probe=None):
-        """Runs the fused pair program; returns the final [nmaps, fh, fw] tensor.
-        x, y: images [n, C, H, W] (for the fused moments); xy0: the initial pair maps
-        (None when the moments are fused into the first conv).  ``probe(idx, op, launch)``
-        (optional) is called after each op with a closure that re-launches it, so a
-        benchmark can time single kernels on live data."""
-        sfx = self._sfx(x.dtype)
-        lib = N.load()
-        dev = x.device
-        nmaps = n1 if diag else n1 * n2
-        vals = {}
-        if xy0 is not None:
-            vals[self.v0] = xy0
-        ops = self.pair_ops
-        last = self._last_use(ops, self.vf)
-        C = x.shape[1]
-        for idx, op in enumerate(ops):
-            ho, wo = op.shape_out
-            if op.kind == "conv":
-                out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
-                g = op.geom
-                h, w = op.shape_in
-                a = N.ConvArgs()
-                if op.pre == N.CGP_PRE_MOMENTS:
-                    a.in_, a.in_y, a.channels = N.ptr(x), N.ptr(y), C
-                else:
-                    a.in_ = N.ptr(vals[op.src])
-                a.out = N.ptr(out)
-                a.addend = N.ptr(vals[op.addend]) if op.addend is not None else None
-                if op.pre == N.CGP_PRE_RELU:
-                    vx, vy = var[op.pre_var]
-                    a.pre_xx, a.pre_yy = N.ptr(vx), N.ptr(vy)
-                if op.post == N.CGP_POST_RELU:
-                    vx, vy = var[op.post_var]
-                    a.post_xx, a.post_yy = N.ptr(vx), N.ptr(vy)
-                a.pre, a.post = op.pre, op.post
-                a.nmaps, a.n1, a.n2 = nmaps, n1, n2
-                a.h, a.w, a.ho, a.wo = h, w, ho, wo
-                a.taps, a.offset, a.stride, a.dilation = g.taps, g.offset, g.stride, g.dilation
-                a.same, a.diag = int(same), int(diag)
-                a.weight, a.bias = g.weight, g.bias
-                a.flags = self.flags
-                fn = getattr(lib, f"cgp_conv_{sfx}")
-                launch = (lambda fn=fn, a=a: N.check(fn(a, stream), "cgp_conv"))
-            elif op.kind in NONLIN_KINDS:
-                out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
-                launch = self._nonlin_launch(
-                    op, sfx, stream, vals[op.src], out, var[op.src], n1, n2, same, diag,
-                    addend=vals[op.addend] if op.addend is not None else None)
-            elif op.kind == "add":
-                out = torch.empty((nmaps, ho, wo), dtype=x.dtype, device=dev)
-                n = nmaps * ho * wo
-                srcs = [(coef, vals[t]) for coef, t in op.terms]
-
-                def launch(srcs=srcs, out=out, n=n):
-                    _axpby_terms(sfx, srcs, out, n, stream)
-            else:
-                raise AssertionError(op.kind)
-            launch()
-            if probe is not None:
-                probe(idx, op, launch)
-            vals[op.dst] = out
-            for v in [v for v in vals if last.get(v, -1) <= idx and v != op.dst]:
-                del vals[v]
-        return vals[self.vf]
-
-    # -- NTK: K and Θ through the unfused program ------------------------------------------
+    # -- pair pipeline: the forward run and the NTK run (K and Θ) ---------------------------
     def ntk_need_var(self) -> set:
         """The values whose variance maps the NTK run reads: every ReLU's, Erf's, Gelu's and
         ABReLU's source in the unfused program (run_variances(need=...))."""
         return {o.src for o in self.prog.ops if o.kind in NONLIN_KINDS}
 
-    def run_pairs_ntk(self, xy0, var, n1, n2, same, diag, stream):
-        """Runs ntk_steps on the pair maps; returns (K, Θ) of the final value as
-        [nmaps, fh, fw] tensors, Θ None when it is zero (a model without a Conv2d).
-        xy0: the input moments' pair maps [nmaps, H, W] (not modified); var: the variance
-        maps of ntk_need_var().
+    def layer_list(self, ntk: bool = False):
+        """(steps, k, theta) of the forward run (layer_steps over pair_ops) or of the NTK run
+        (ntk_steps over the unfused program), lowered and scheduled once per plan."""
+        key = "_ntk_steps" if ntk else "_layer_steps"
+        if key not in self.__dict__:
+            self.__dict__[key] = ntk_steps(self.prog, self.v0, self.vf) if ntk else \
+                layer_steps(self.prog, self.pair_ops, self.v0, self.vf)
+        return self.__dict__[key]
 
-        Buffers are freed after their last reader, as in run_pairs.  Peak live pair maps:
-        4 on a Conv2d/ReLU chain (K, Θ and K', Θ' of a cgp_relu_ntk_*, cgp_erf_* or cgp_gelu_*
-        step;
-        3 at a conv's Θ launch), plus 2 (K and Θ) for every Sum / Mixture branch result or skip value
-        waiting for its sum -- 6 inside a residual block of the ResNets."""
-        sfx = self._sfx(xy0.dtype)
-        lib = N.load()
-        dev = xy0.device
+    def run_layer_steps(self, steps, x, y, xy0, var, n1, n2, same, diag, stream):
+        """Runs a layer-path list (layer_list) on the pair maps; returns (K, Θ) of the final
+        value as [nmaps, fh, fw] tensors, Θ None for the forward list and where it is zero (a
+        model without a Conv2d).  x, y: images [n, C, H, W] (read by a conv whose pre-stage is
+        the moments); xy0: the input moments' pair maps [nmaps, H, W] (not modified; None when
+        the moments are fused into the first conv); var: the variance maps of need_var, of
+        ntk_need_var() for the NTK list.
+
+        Every output is allocated at the step that writes it and dropped with the step's
+        ``free``, after its last reader.  Peak live pair maps of the NTK run: 4 on a
+        Conv2d/ReLU chain (K, Θ and K', Θ' of a cgp_relu_ntk_*, cgp_erf_* or cgp_gelu_* step;
+        3 at a conv's Θ launch), plus 2 (K and Θ) for every Sum / Mixture branch result or skip
+        value waiting for its sum -- 6 inside a residual block of the ResNets."""
+        steps, kbuf, tbuf = steps
+        sfx = self._sfx(x.dtype)
+        conv = getattr(N.load(), f"cgp_conv_{sfx}")
         nmaps = n1 if diag else n1 * n2
-        if "_ntk_steps" not in self.__dict__:
-            self._ntk_steps = ntk_steps(self.prog, self.v0, self.vf)
-        steps, kbuf, tbuf = self._ntk_steps
-        last = {}
-        for idx, st in enumerate(steps):
-            for b in st.reads():
-                last[b] = idx
-        last[kbuf] = len(steps)
-        if tbuf is not None:
-            last[tbuf] = len(steps)
-        bufs = {("K", self.v0): xy0}
-
-        def new(op):
-            return torch.empty((nmaps,) + tuple(op.shape_out), dtype=xy0.dtype, device=dev)
-
-        for idx, st in enumerate(steps):
+        same, diag = int(same), int(diag)
+        bufs = {} if xy0 is None else {("K", self.v0): xy0}
+        dtype, dev = x.dtype, x.device
+        for st in steps:
             op = st.op
-            ho, wo = op.shape_out
+            shape = (nmaps, *op.shape_out)
+            out = bufs[st.dst] = torch.empty(shape, dtype=dtype, device=dev)
             if st.fn == "conv":
-                out = bufs[st.dst] = new(op)
-                g = op.geom
-                a = N.ConvArgs()
-                a.in_, a.out = N.ptr(bufs[st.src]), N.ptr(out)
-                a.addend = N.ptr(bufs[st.addend]) if st.addend is not None else None
-                a.pre, a.post = N.CGP_PRE_NONE, N.CGP_POST_NONE
-                a.nmaps, a.n1, a.n2 = nmaps, n1, n2
-                (a.h, a.w), a.ho, a.wo = op.shape_in, ho, wo
-                a.taps, a.offset, a.stride, a.dilation = g.taps, g.offset, g.stride, g.dilation
-                a.same, a.diag = int(same), int(diag)
-                a.weight, a.bias = g.weight, st.bias
-                a.flags = self.flags
-                N.check(getattr(lib, f"cgp_conv_{sfx}")(a, stream), "cgp_conv")
-            elif st.fn.removesuffix("_ntk") in NONLIN_KINDS:
-                out = bufs[st.dst] = new(op)
-                two = st.fn.endswith("_ntk")
-                tout = None
-                if two:
-                    tout = bufs[st.dst_theta] = new(op)
-                self._nonlin_launch(op, sfx, stream, bufs[st.src], out, var[st.var], n1, n2, same,
-                                    diag, theta=bufs[st.theta] if two else None,
-                                    out_theta=tout)()
+                a = self._conv_args(op, bufs.get(st.src), out, nmaps, n1, n2, same, diag,
+                                    self.flags, st.bias, bufs.get(st.addend), var, (x, y))
+                N.check(conv(a, stream), "cgp_conv")
             elif st.fn == "axpby":
-                out = bufs[st.dst] = new(op)
-                _axpby_terms(sfx, [(c, bufs[b]) for c, b in st.terms], out, nmaps * ho * wo,
-                             stream)
+                _axpby_terms(sfx, [(c, bufs[b]) for c, b in st.terms], out, out.numel(), stream)
             else:
-                raise AssertionError(st.fn)
-            for b in [b for b in bufs if last.get(b, -1) <= idx and b not in st.writes()]:
+                tout = None
+                if st.dst_theta is not None:
+                    tout = bufs[st.dst_theta] = torch.empty(shape, dtype=dtype, device=dev)
+                self._nonlin_launch(op, sfx, stream, bufs[st.src], out, var[st.var], n1, n2,
+                                    same, diag, addend=bufs.get(st.addend),
+                                    theta=bufs.get(st.theta), out_theta=tout)
+            for b in st.free:
                 del bufs[b]
         return bufs[kbuf], (None if tbuf is None else bufs[tbuf])
 

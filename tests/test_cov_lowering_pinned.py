@@ -1,5 +1,5 @@
 """CPU-only: the lowering onto position-pair maps (program.pool_steps, pool_ntk_steps), pinned
-step by step to what the commit before the two lists shared one record type (CovStep) and one
+step by step to what the commit before the two lists shared one record type (Step) and one
 scheduling helper gave.  The literals were recorded there; on that commit a forward step had no
 ``bias`` of its own, and the geometry's (op.geom.bias of a conv or corrconv step, None
 elsewhere) was recorded in its place.
