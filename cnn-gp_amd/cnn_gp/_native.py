@@ -183,6 +183,18 @@ class ABReluCovArgs(ctypes.Structure):
     ]
 
 
+class SinArgs(ctypes.Structure):
+    """Mirror of cgp_sin_args (include/cnngp.h): cgp_erf_args' fields, then A, B, C, D."""
+    _fields_ = list(ErfArgs._fields_) + [("A", _f64), ("B", _f64), ("C", _f64), ("D", _f64)]
+
+
+class SinCovArgs(ctypes.Structure):
+    """Mirror of cgp_sin_cov_args (include/cnngp.h): cgp_abrelu_cov_args' maps, then A, B, C,
+    D."""
+    _fields_ = ABReluCovArgs._fields_[:-3] + [("A", _f64), ("B", _f64), ("C", _f64),
+                                              ("D", _f64)]
+
+
 class NetOp(ctypes.Structure):
     """Mirror of cgp_net_op (include/cnngp.h)."""
     _fields_ = [
@@ -307,6 +319,16 @@ SIGNATURES = {
     "cgp_abrelu_cov_args_size": (ctypes.c_size_t, []),
     "cgp_abrelu_cov_f64": (_i32, [ctypes.POINTER(ABReluCovArgs), _vp]),
     "cgp_abrelu_cov_f32": (_i32, [ctypes.POINTER(ABReluCovArgs), _vp]),
+    "cgp_sin_args_size": (ctypes.c_size_t, []),
+    "cgp_sin_f64": (_i32, [ctypes.POINTER(SinArgs), _vp]),
+    "cgp_sin_f32": (_i32, [ctypes.POINTER(SinArgs), _vp]),
+    "cgp_var_sin_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _f64, _f64, _f64, _f64,
+                               _vp, _vp, _vp]),
+    "cgp_var_sin_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _f64, _f64, _f64, _f64,
+                               _vp, _vp, _vp]),
+    "cgp_sin_cov_args_size": (ctypes.c_size_t, []),
+    "cgp_sin_cov_f64": (_i32, [ctypes.POINTER(SinCovArgs), _vp]),
+    "cgp_sin_cov_f32": (_i32, [ctypes.POINTER(SinCovArgs), _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_axpby_f32": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_scale_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _f64, _vp]),
@@ -386,6 +408,8 @@ def load():
                 lib.cgp_gelu_cov_args_size() != ctypes.sizeof(GeluCovArgs) or \
                 lib.cgp_abrelu_args_size() != ctypes.sizeof(ABReluArgs) or \
                 lib.cgp_abrelu_cov_args_size() != ctypes.sizeof(ABReluCovArgs) or \
+                lib.cgp_sin_args_size() != ctypes.sizeof(SinArgs) or \
+                lib.cgp_sin_cov_args_size() != ctypes.sizeof(SinCovArgs) or \
                 lib.cgp_covntk_nonlin_args_size() != ctypes.sizeof(CovNonlinNtkArgs) or \
                 lib.cgp_covntk_conv_args_size() != ctypes.sizeof(CovConvNtkArgs) or \
                 lib.cgp_net_op_size() != ctypes.sizeof(NetOp) or \

@@ -27,6 +27,7 @@ VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
 NTK_MAPS_FUSED = True
 
 __all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "Gelu", "ABReLU", "LeakyReLU",
+           "Sin", "Cos", "Rbf",
            "GlobalAvgPool", "AvgPool2d",
            "CorrelatedConv2d", "rbf_corr", "band_corr", "Sequential", "Mixture", "Sum",
            "resnet_block")
@@ -200,6 +201,9 @@ class NNGPKernel(nn.Module):
             elif isinstance(m, ABReLU):
                 # the slopes are in the op records: a plan serves one (a, b)
                 key.append(("ab", float(d["a"]), float(d["b"])))
+            elif isinstance(m, Sin):
+                # the constants are in the op records: a plan serves one (A, B, C, D)
+                key.append(("sin", *m.constants()))
             elif isinstance(m, Mixture):
                 mixture = True
                 key.append(("m", tuple(m.proportions())))
@@ -255,7 +259,7 @@ class NNGPKernel(nn.Module):
         """Evaluate the ReLU map op by op exactly like the reference (correctly rounded
         1/sqrt, sqrt, acos, division) instead of the closed form (default; within 1e-14 of
         the exact map, see csrc/relu_poly.h).  For parity studies; ~2x slower.  An Erf and
-        a Gelu have one evaluation mode and ignore it; an ABReLU / LeakyReLU evaluates the
+        a Gelu have one evaluation mode and ignore it, and so does a Sin / Cos / Rbf; an ABReLU / LeakyReLU evaluates the
         ReLU map inside it in the chosen mode."""
         for m in self.modules():
             m.__dict__["_cgp_exact_relu"] = bool(enabled)
@@ -351,6 +355,10 @@ class NNGPKernel(nn.Module):
             ABReLU(a, b)    K' as forward,         Θ' = Θ·κ̇,  κ̇ = (a − b)²·(π - θ)/2π + ab
                             with the ReLU's θ; Θ' = Θ·(a² + b²)/2 where K' is overridden
                             
+            Sin(a, b, θ)    K' as forward,         Θ' = Θ·κ̇,  κ̇ = D·(e_d + C·e_s) with
+                            e_d = exp(−B·(v₁ + v₂ − 2c)), e_s = exp(−B·(v₁ + v₂ + 2c)) and
+                            (B, C, D) = (b²/2, cos 2θ, a²b²/2); κ̇ = D·(1 + C·exp(−4B·v)) where
+                            K' is overridden; Cos is θ = π/2, Rbf(γ) is κ̇ = 2γ·K'  
             Sum / Mixture   the same (weighted) sum on both
 
         and the result is Θ of the final 1x1 value; a model without a Conv2d gives zeros
@@ -495,7 +503,8 @@ class NNGPKernel(nn.Module):
         """The neural tangent kernel Θ, [N1, N2] (or [N1] when diag), carried on position-pair
         maps; with ``return_nngp`` the pair (K, Θ).  Valid for every model forward runs on
         position-pair maps -- a GlobalAvgPool, AvgPool2d or CorrelatedConv2d anywhere the
-        forward rules allow, with ReLU, Erf, Gelu and ABReLU -- and for a model with none of them,
+        forward rules allow, with ReLU, Erf, Gelu, ABReLU and Sin / Cos / Rbf -- and for a model
+        with none of them,
         where it is a second, slower route to ``ntk``'s result.
 
         The recursion is ntk's, with the pooling layers the same linear op on both streams
@@ -503,6 +512,7 @@ class NNGPKernel(nn.Module):
 
             Conv2d, CorrelatedConv2d   K' = A(K) + var_bias,  Θ' = A(Θ) + K'
             ReLU / Erf / Gelu / ABReLU K' as forward,         Θ' = Θ·κ̇   (ntk's κ̇ of
+            / Sin / Cos / Rbf
                                        (S[p, q], xx_i[p], yy_j[q]); the override's value
                                        where same, i = j and p = q)
             AvgPool2d, GlobalAvgPool   the same average of K and of Θ
@@ -790,6 +800,76 @@ class LeakyReLU(ABReLU):
 
     def extra_repr(self):
         return f"negative_slope={self.a}"
+
+
+class Sin(NNGPKernel):
+    """The sinusoid φ(x) = a·sin(b·x + phase) (no reference counterpart): the layer kernel of
+    sine networks and of random Fourier features, a function of the distance d = v₁ + v₂ − 2c
+    and of s = v₁ + v₂ + 2c,
+    K' = A·(exp(−B·d) − C·exp(−B·s)),  κ̇ = D·(exp(−B·d) + C·exp(−B·s)),
+    (A, B, C, D) = (a²/2, b²/2, cos(2·phase), a²b²/2), and A·(1 − C·exp(−4B·v)) where the ReLU
+    overrides (device: SinMap).  Usable wherever ABReLU is: forward, ntk,
+    position_covariance, the pooled path and ntk_maps; a model with one runs on the layer path,
+    and set_exact_relu has no effect on it.  ``a``, ``b`` and ``phase`` are plain floats:
+    assigning one takes effect at the next call.  |K'| <= a²; the map is not homogeneous."""
+
+    def __init__(self, a=1.0, b=1.0, phase=0.0):
+        super().__init__()
+        self.a = float(a)
+        self.b = float(b)
+        self.phase = float(phase)
+        self.constants()
+
+    def constants(self):
+        """(A, B, C, D) = (a²/2, b²/2, cos(2·phase), a²b²/2) in double: what the kernels take."""
+        a, b, phase = float(self.a), float(self.b), float(self.phase)
+        name = type(self).__name__
+        if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(phase)):
+            raise ValueError(f"{name}: a, b and phase must be finite, got ({a}, {b}, {phase})")
+        if a == 0.0 or b == 0.0:
+            raise ValueError(f"{name}: a and b must not be zero (φ is constant), got ({a}, {b})")
+        consts = (a * a / 2, b * b / 2, math.cos(2 * phase), a * a * b * b / 2)
+        if not all(math.isfinite(c) and c != 0.0 for c in (consts[0], consts[1], consts[3])):
+            raise ValueError(f"{name}: a² or b² leaves the double range, got ({a}, {b})")
+        return consts
+
+    def layers(self):
+        return 0
+
+    def extra_repr(self):
+        return f"a={self.a}, b={self.b}, phase={self.phase}"
+
+
+class Cos(Sin):
+    """φ(x) = a·cos(b·x): Sin(a, b, π/2), bit for bit (cos π is exactly −1)."""
+
+    def __init__(self, a=1.0, b=1.0):
+        super().__init__(a, b, math.pi / 2)
+
+    def extra_repr(self):
+        return f"a={self.a}, b={self.b}"
+
+
+class Rbf(Sin):
+    """The squared-exponential layer kernel K' = exp(−gamma·(v₁ + v₂ − 2c)), κ̇ = 2·gamma·K',
+    variance 1: that of the random Fourier feature φ(x) = √2·sin(√(2·gamma)·x + π/4), with the
+    constants set to (1, gamma, 0, 2·gamma) so that C is exactly 0 and the kernel evaluates one
+    exponential.  K' lies in (0, 1].  ``gamma`` is a plain float: assigning it takes effect at
+    the next call."""
+
+    def __init__(self, gamma=1.0):
+        NNGPKernel.__init__(self)
+        self.gamma = float(gamma)
+        self.constants()
+
+    def constants(self):
+        g = float(self.gamma)
+        if not (math.isfinite(g) and g > 0.0 and math.isfinite(2 * g)):
+            raise ValueError(f"Rbf: gamma must be positive and finite, got {g}")
+        return 1.0, g, 0.0, 2 * g
+
+    def extra_repr(self):
+        return f"gamma={self.gamma}"
 
 
 class GlobalAvgPool(NNGPKernel):

@@ -10,6 +10,7 @@ whole [N1·N2, 1, H, W] covariance tensor.  Here the tree is flattened once into
     v  = erf(u)                      Erf (no reference counterpart)
     v  = gelu(u)                     Gelu (no reference counterpart)
     v  = abrelu(u; a, b)             ABReLU / LeakyReLU (no reference counterpart)
+    v  = sin(u; A, B, C, D)          Sin / Cos / Rbf (no reference counterpart)
     v  = add[(coef, u), ...]         Sum (kernels.py:252-254) / Mixture (:220-225)
     v  = pool(u)                     GlobalAvgPool (no reference counterpart; DESIGN §3.3:
                                      such a program runs on position-pair maps, pool_steps)
@@ -22,12 +23,13 @@ and then split into two device pipelines:
 
 * the VARIANCE pipeline runs every op, unfused, on the per-image maps [xx | yy]
   ((N1 + N2) maps — negligible next to the N1·N2 pair maps) and keeps the variances
-  of every value a ReLU, Erf, Gelu or ABReLU consumes;
+  of every value a ReLU, Erf, Gelu, ABReLU or Sin consumes;
 * the PAIR pipeline runs on the N1·N2 maps with ops fused so each HBM pass does the
   most work:  [ReLU|moments] → Conv → [ReLU] → [+ addend]  is ONE kernel
   (cgp_conv_*), a ReLU not adjacent to a single-use conv is cgp_relu_* (+ addend),
-  an Erf, a Gelu or an ABReLU is always its own pass cgp_erf_* / cgp_gelu_* / cgp_abrelu_*
-  (+ addend), and only sums that cannot be folded into their producer run as cgp_axpby_*.
+  an Erf, a Gelu, an ABReLU or a Sin is always its own pass cgp_erf_* / cgp_gelu_* /
+  cgp_abrelu_* / cgp_sin_* (+ addend), and only sums that cannot be folded into their producer
+  run as cgp_axpby_*.
 
 Fusion changes no arithmetic: each fused stage performs exactly the operations of the
 op it replaces (a + b == b + a in IEEE, so folding a Sum into either branch is exact).
@@ -78,8 +80,8 @@ class CorrGeom(ConvGeom):
 
 @dataclasses.dataclass
 class Op:
-    # 'conv' | 'relu' | 'erf' | 'gelu' | 'abrelu' | 'add' | 'pool' | 'avgpool' | 'corrconv' |
-    # 'moments'
+    # 'conv' | 'relu' | 'erf' | 'gelu' | 'abrelu' | 'sin' | 'add' | 'pool' | 'avgpool' |
+    # 'corrconv' | 'moments'
     kind: str
     dst: int
     src: Optional[int] = None
@@ -97,6 +99,8 @@ class Op:
     # ((a − b)², a·b, (a² + b²)/2), computed in double
     slopes: Optional[tuple] = None
     smh: Optional[tuple] = None
+    # sin: the kernels' constants (A, B, C, D) = (a²/2, b²/2, cos 2θ, a²b²/2), computed in double
+    consts: Optional[tuple] = None
 
 
 class Program:
@@ -191,13 +195,15 @@ def _emit(prog: Program, mod, v: int) -> int:
         prog.ops.append(Op("conv", out, src=v, geom=conv_geometry(mod), shape_in=(h, w),
                            shape_out=(ho, wo)))
         return out
-    # one table from module class to elementwise kind (LeakyReLU is an ABReLU)
+    # one table from module class to elementwise kind (LeakyReLU is an ABReLU; Cos and Rbf
+    # are Sins)
     kind = next((k for cls, k in ((K.ReLU, "relu"), (K.Erf, "erf"), (K.Gelu, "gelu"),
-                                  (K.ABReLU, "abrelu")) if isinstance(mod, cls)), None)
+                                  (K.ABReLU, "abrelu"), (K.Sin, "sin"))
+                 if isinstance(mod, cls)), None)
     if kind is not None:
         out = prog.new_value(prog.shapes[v])
         consts = dict(slopes=(float(mod.a), float(mod.b)), smh=mod.constants()) \
-            if kind == "abrelu" else {}
+            if kind == "abrelu" else dict(consts=mod.constants()) if kind == "sin" else {}
         prog.ops.append(Op(kind, out, src=v, shape_in=prog.shapes[v], shape_out=prog.shapes[v],
                            **consts))
         return out
@@ -265,8 +271,8 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
          fold_moments: bool = True) -> list:
     """Return the fused op list for the pair pipeline (prog.ops is left untouched).
     ``pre_relu`` / ``fold_moments`` enable rules 3 / 4 (the whole-network kernel keeps
-    standalone ReLU and moments ops: in LDS they cost no extra memory pass).  An erf, gelu or
-    abrelu op is never a conv's pre- or post-stage (rules 1 and 3 match ReLU only); rule 2 may
+    standalone ReLU and moments ops: in LDS they cost no extra memory pass).  An erf, gelu,
+    abrelu or sin op is never a conv's pre- or post-stage (rules 1 and 3 match ReLU only); rule 2 may
     give it an addend."""
     ops = [dataclasses.replace(o, terms=list(o.terms)) for o in prog.ops]
     if not enable:
@@ -303,7 +309,7 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
             (_, t0), (_, t1) = a.terms
             for cand, other in ((t1, t0), (t0, t1)):
                 pi = producer(ops, cand)
-                if pi is None or ops[pi].kind not in ("conv", "relu", "erf", "gelu", "abrelu") or \
+                if pi is None or ops[pi].kind not in ("conv",) + NONLIN_KINDS or \
                         ops[pi].addend is not None or uses.get(cand, 0) != 1:
                     continue
                 oi = producer(ops, other)
@@ -350,18 +356,22 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
 
 
 # the op kinds that read the per-image variances of their source
-NONLIN_KINDS = ("relu", "erf", "gelu", "abrelu")
+NONLIN_KINDS = ("relu", "erf", "gelu", "abrelu", "sin")
 
 # The layer-path entry point cgp_<name>_* of every nonlinearity: its argument class, that
-# class's K' output field, whether the record takes the ReLU evaluation flags and the op's
-# (s, m, h), and what cgp_var_<kind>_* takes between `same` and its outputs.  The ReLU alone
+# class's K' output field, whether the record takes the ReLU evaluation flags, the record's
+# fields for the op's constants (an abrelu's (s, m, h), a sin's (A, B, C, D)), and what
+# cgp_var_<kind>_* takes between `same` and its outputs.  The ReLU alone
 # has an entry point of its own for the two-stream form; the others take theta or NULL.
 NONLIN_CALLS = {
-    "relu": (N.ReluArgs, "out", True, False, lambda op: ()),
-    "relu_ntk": (N.ReluNtkArgs, "out_xy", True, False, None),
-    "erf": (N.ErfArgs, "out_xy", False, False, lambda op: ()),
-    "gelu": (N.GeluArgs, "out_xy", False, False, lambda op: ()),
-    "abrelu": (N.ABReluArgs, "out_xy", True, True, lambda op: (op.smh[2],)),
+    "relu": (N.ReluArgs, "out", True, None, lambda op: ()),
+    "relu_ntk": (N.ReluNtkArgs, "out_xy", True, None, None),
+    "erf": (N.ErfArgs, "out_xy", False, None, lambda op: ()),
+    "gelu": (N.GeluArgs, "out_xy", False, None, lambda op: ()),
+    "abrelu": (N.ABReluArgs, "out_xy", True, lambda op: zip("smh", op.smh),
+               lambda op: (op.smh[2],)),
+    "sin": (N.SinArgs, "out_xy", False, lambda op: zip("ABCD", op.consts),
+            lambda op: op.consts),
 }
 
 
@@ -403,6 +413,9 @@ class Step:
     fn "abrelu":   dst = abrelu(src; op.smh) [+ addend], variances of ``var``
                                                                          cgp_abrelu_* (theta NULL)
     fn "abrelu_ntk": dst, dst_theta = abrelu(src), theta·κ̇               cgp_abrelu_*
+    fn "sin":      dst = sin(src; op.consts) [+ addend], variances of ``var``
+                                                                         cgp_sin_* (theta NULL)
+    fn "sin_ntk":  dst, dst_theta = sin(src), theta·κ̇                    cgp_sin_*
     fn "axpby":    dst = Σ coef·buffer over ``terms`` (coef None: 1)     cgp_axpby_*
 
     Either list on position-pair maps may hold
@@ -416,6 +429,8 @@ class Step:
                                                                          cgp_gelu_cov_*
     fn "abrelu":  dst = abrelu of src (op.smh), variances of value ``var`` [+ addend]
                                                                          cgp_abrelu_cov_*
+    fn "sin":     dst = sin of src (op.consts), variances of value ``var`` [+ addend]
+                                                                         cgp_sin_cov_*
     fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
     fn "avgpool": dst = mean of src over the windows of p and of q (op.geom)
                                                                          cgp_covmap_avgpool_*
@@ -431,6 +446,8 @@ class Step:
                                                                           cgp_covntk_nonlin_*
     fn "abrelu_ntk": dst, dst_theta = abrelu of src [+ addend], theta·κ̇ [+ addend_theta]
                                                                           cgp_abrelu_cov_*
+    fn "sin_ntk":    dst, dst_theta = sin of src [+ addend], theta·κ̇ [+ addend_theta]
+                                                                          cgp_sin_cov_*
     fn "accum":      dst = dst + src, in place                            cgp_axpby_*"""
     fn: str
     dst: object
@@ -535,11 +552,12 @@ def ntk_steps(prog: Program, v0: int, vf: int):
         Erf             K' = erf(K),           Θ' = Θ·κ̇,  κ̇ = (4/π)/√D  
         Gelu            K' = gelu(K),          Θ' = Θ·κ̇,  κ̇ = E[φ'φ']   
         ABReLU          K' = abrelu(K),        Θ' = Θ·κ̇,  κ̇ = s·(π - θ)/2π + m  
+        Sin             K' = sin(K),           Θ' = Θ·κ̇,  κ̇ = D·(e_d + C·e_s)   
         Sum / Mixture   the same (weighted) sum on both streams
 
     A zero Θ is carried as None and costs nothing: the first conv's Θ' IS its K' (the same
-    buffer), a ReLU / Erf / Gelu / ABReLU on a value with Θ = 0 is the plain cgp_relu_* /
-    forward-only cgp_erf_* / cgp_gelu_* / cgp_abrelu_*, sums skip zero terms
+    buffer), a ReLU / Erf / Gelu / ABReLU / Sin on a value with Θ = 0 is the plain cgp_relu_* /
+    forward-only cgp_erf_* / cgp_gelu_* / cgp_abrelu_* / cgp_sin_*, sums skip zero terms
     (a sum whose only non-zero term has weight 1 passes that term's buffer on)."""
     steps = []
     theta = {v0: None}
@@ -590,6 +608,8 @@ GELU_RULE_GLOBAL = ("a Gelu downstream of a GlobalAvgPool is not implemented: it
                     "the pooled self-covariances of each image (DESIGN §8)")
 ABRELU_RULE_GLOBAL = ("an ABReLU / LeakyReLU downstream of a GlobalAvgPool is not implemented: "
                       "it would need the pooled self-covariances of each image (DESIGN §8)")
+SIN_RULE_GLOBAL = ("a Sin / Cos / Rbf downstream of a GlobalAvgPool is not implemented: it would "
+                   "need the pooled self-covariances of each image (DESIGN §8)")
 CORRCONV_RULE_NTK = ("ntk: the neural tangent kernel of a model with a CorrelatedConv2d is not "
                      "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
 
@@ -631,7 +651,8 @@ class CovSteps:
 
 # op kind -> the rule it breaks downstream of a GlobalAvgPool (its result is not pooled)
 POOL_RULES = {"relu": POOL_RULE_NONLIN, "erf": POOL_RULE_NONLIN, "gelu": GELU_RULE_GLOBAL,
-              "abrelu": ABRELU_RULE_GLOBAL, "avgpool": AVGPOOL_RULE_GLOBAL, "corrconv": CORRCONV_RULE_GLOBAL}
+              "abrelu": ABRELU_RULE_GLOBAL, "sin": SIN_RULE_GLOBAL,
+              "avgpool": AVGPOOL_RULE_GLOBAL, "corrconv": CORRCONV_RULE_GLOBAL}
 
 
 def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
@@ -647,8 +668,8 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
     variances are the diagonal of the conv's output on the self pairs, which has to exist
     as a map to be read.
 
-    Raises NotImplementedError naming the rule for a ReLU / Erf, a Gelu, an ABReLU, an AvgPool2d
-    or a CorrelatedConv2d after a GlobalAvgPool and for a path that does not pass exactly one
+    Raises NotImplementedError naming the rule for a ReLU / Erf, a Gelu, an ABReLU, a Sin, an
+    AvgPool2d or a CorrelatedConv2d after a GlobalAvgPool and for a path that does not pass exactly one
     GlobalAvgPool."""
     pooled = {v0: False}
     avgpooled = {v0: False}
@@ -698,7 +719,7 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
             steps.append(Step("nonlin", op.dst, src=op.src, op=op,
                                  post=N.CGP_COV_RELU if op.kind == "relu" else N.CGP_COV_ERF,
                                  var=op.src, addend=op.addend))
-        elif op.kind in ("gelu", "abrelu"):
+        elif op.kind in ("gelu", "abrelu", "sin"):
             steps.append(Step(op.kind, op.dst, src=op.src, op=op, var=op.src,
                                  addend=op.addend))
         elif op.kind in ("pool", "avgpool"):
@@ -745,8 +766,8 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
         Conv2d, CorrelatedConv2d   K' = A(K) + b,   Θ' = A(Θ) + K'   (correlated weights are a
                                    fixed linear map of i.i.d. parameters: the conv's rule, A_R)
         ReLU / Erf / Gelu          K' as forward,   Θ' = Θ·κ̇
-        ABReLU                     K' as forward,   Θ' = Θ·κ̇   (cgp_abrelu_cov_* with theta: a
-                                   launch of its own, never a conv's post-stage)
+        ABReLU, Sin                K' as forward,   Θ' = Θ·κ̇   (cgp_abrelu_cov_* / cgp_sin_cov_*
+                                   with theta: a launch of its own, never a conv's post-stage)
         AvgPool2d, GlobalAvgPool   the same linear op on both
         Sum / Mixture              the same (weighted) sum on both
 
@@ -830,14 +851,14 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
                              var=st.var, addend=ka, theta=ts, dst_theta=("T", d),
                              addend_theta=ta), shape, sc)
                 theta[d] = ("T", d)
-        elif st.fn == "abrelu":
+        elif st.fn in ("abrelu", "sin"):
             # a launch of its own on either run: one entry point, with and without Θ
             if ts is None:
-                emit(Step("abrelu", K(d), src=K(st.src), op=op, var=st.var, addend=ka),
+                emit(Step(st.fn, K(d), src=K(st.src), op=op, var=st.var, addend=ka),
                      shape, sc)
                 theta[d] = ta
             else:
-                emit(Step("abrelu_ntk", K(d), src=K(st.src), op=op, var=st.var, addend=ka,
+                emit(Step(st.fn + "_ntk", K(d), src=K(st.src), op=op, var=st.var, addend=ka,
                              theta=ts, dst_theta=("T", d), addend_theta=ta), shape, sc)
                 theta[d] = ("T", d)
         elif st.fn in ("pool", "avgpool"):
@@ -936,7 +957,7 @@ class Plan:
         """Fills the argument record of a layer-path nonlinearity (NONLIN_CALLS) and launches
         it; with ``theta`` the two-stream form (Θ' = Θ·κ̇)."""
         name = "relu_ntk" if op.kind == "relu" and theta is not None else op.kind
-        cls, out_field, has_flags, has_smh = NONLIN_CALLS[name][:4]
+        cls, out_field, has_flags, consts = NONLIN_CALLS[name][:4]
         vx, vy = var
         ho, wo = op.shape_out
         r = cls()
@@ -949,8 +970,8 @@ class Plan:
         r.xx, r.yy = N.ptr(vx), N.ptr(vy)
         r.nmaps, r.n1, r.n2 = (n1 if diag else n1 * n2), n1, n2
         r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
-        if has_smh:
-            r.s, r.m, r.h = op.smh
+        for field, value in consts(op) if consts else ():
+            setattr(r, field, value)
         if has_flags:
             r.flags = self.flags
         N.check(getattr(N.load(), f"cgp_{name}_{sfx}")(r, stream), "cgp_" + name)
@@ -999,7 +1020,7 @@ class Plan:
 
     # -- variance pipeline --------------------------------------------------------------
     def run_variances(self, xx0, yy0, n1, n2, same, stream, need=None):
-        """Per-image variance maps of every value a ReLU, Erf, Gelu or ABReLU reads (or of
+        """Per-image variance maps of every value a ReLU, Erf, Gelu, ABReLU or Sin reads (or of
         ``need``).
         xx0/yy0: [n, H, W]."""
         sfx = self._sfx(xx0.dtype)
@@ -1062,7 +1083,7 @@ class Plan:
         """cgp_var_op records of the variance program (cached per need/quarter/device):
         LDS slots by first fit over the values' live ranges, store offsets per image.
         None when the program has an op the chain kernel lacks (a Sum of > 4 terms, an
-        Erf, a Gelu, an ABReLU).  The records are uploaded once per plan, need set and device, and the
+        Erf, a Gelu, an ABReLU, a Sin).  The records are uploaded once per plan, need set and device, and the
         copy is synchronous (on the uploading stream alone, not the device): the records are
         shared by every stream that runs the plan, and none may see a copy in flight."""
         key = (frozenset(need), frozenset(quarter), str(dev))
@@ -1207,8 +1228,8 @@ class Plan:
 
     # -- pair pipeline: the forward run and the NTK run (K and Θ) ---------------------------
     def ntk_need_var(self) -> set:
-        """The values whose variance maps the NTK run reads: every ReLU's, Erf's, Gelu's and
-        ABReLU's source in the unfused program (run_variances(need=...))."""
+        """The values whose variance maps the NTK run reads: every ReLU's, Erf's, Gelu's,
+        ABReLU's and Sin's source in the unfused program (run_variances(need=...))."""
         return {o.src for o in self.prog.ops if o.kind in NONLIN_KINDS}
 
     def layer_list(self, ntk: bool = False):
@@ -1436,6 +1457,10 @@ class Plan:
                         r = pairwise(maps(N.ABReluCovArgs(), st), st)
                         r.s, r.m, r.hh = st.op.smh
                         r.flags = flags
+                    elif st.fn in ("sin", "sin_ntk"):
+                        what = "cgp_sin_cov"
+                        r = pairwise(maps(N.SinCovArgs(), st), st)
+                        r.A, r.B, r.C, r.D = st.op.consts
                     elif st.fn == "avgpool":
                         what = "cgp_covmap_avgpool"
                         r = maps(N.CovAvgPoolArgs(), st)

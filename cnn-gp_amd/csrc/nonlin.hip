@@ -1,7 +1,7 @@
-// nonlin.hip — the entry points of every nonlinearity: ReLU, erf, GELU and the two-slope ReLU
-// on pair maps (cgp_relu_*, cgp_relu_ntk_*, cgp_erf_*, cgp_gelu_*, cgp_abrelu_*), on the
-// per-image variances (cgp_var_*) and on position-pair maps (cgp_cov_nonlin_*,
-// cgp_covntk_nonlin_*, cgp_gelu_cov_*, cgp_abrelu_cov_*).  The kernels and the maps are
+// nonlin.hip — the entry points of every nonlinearity: ReLU, erf, GELU, the two-slope ReLU
+// and the sinusoid on pair maps (cgp_relu_*, cgp_relu_ntk_*, cgp_erf_*, cgp_gelu_*,
+// cgp_abrelu_*, cgp_sin_*), on the per-image variances (cgp_var_*) and on position-pair maps
+// (cgp_cov_nonlin_*, cgp_covntk_nonlin_*, cgp_gelu_cov_*, cgp_abrelu_cov_*, cgp_sin_cov_*).  The kernels and the maps are
 // nonlin_walk.h's; here each layout has one check and one launch, named by the entry point
 // for the messages.  Every check returns CGP_EINVAL before any HIP call.
 
@@ -27,6 +27,19 @@ ABReluMap<T> abrelu_map(double s, double m, double h, int flags) {
     return ABReluMap<T>{(T)s, (T)m, (T)h, exact_relu(flags)};
 }
 
+// the sinusoid's constants (A, B, C, D) = (a²/2, b²/2, cos 2θ, a²b²/2)
+int sin_check(const char* name, double A, double B, double C, double D) {
+    if (!(std::isfinite(A) && std::isfinite(B) && std::isfinite(C) && std::isfinite(D)))
+        return fail(CGP_EINVAL, "%s: A, B, C or D is not finite", name);
+    if (!(A > 0 && B > 0 && std::fabs(C) <= 1))
+        return fail(CGP_EINVAL, "%s: needs A > 0, B > 0 and |C| <= 1", name);
+    return CGP_OK;
+}
+template <typename T>
+SinMap<T> sin_map(double A, double B, double C, double D) {
+    return SinMap<T>{(T)A, (T)B, (T)C, (T)D};
+}
+
 // ----------------------------------------------------------------------------------
 // the layer path.  theta == NULL is the forward-only form.
 // ----------------------------------------------------------------------------------
@@ -41,7 +54,7 @@ struct PairArgs {
     int64_t nmaps, n1, n2;
     int32_t hw, same, diag;
 };
-// of cgp_erf_args, cgp_gelu_args, cgp_abrelu_args; a NULL record gives NULL fields
+// of cgp_erf_args, cgp_gelu_args, cgp_abrelu_args, cgp_sin_args; a NULL record gives NULL fields
 template <class A>
 PairArgs pair_args(const A* a) {
     if (!a) return PairArgs{};
@@ -145,6 +158,13 @@ int abrelu_impl(const cgp_abrelu_args* a, void* stream) {
     if (!finite3(a->s, a->m, a->h)) return fail(CGP_EINVAL, "abrelu: s, m or h is not finite");
     return pair_launch<T>(c, abrelu_map<T>(a->s, a->m, a->h, a->flags), stream);
 }
+template <typename T>
+int sin_impl(const cgp_sin_args* a, void* stream) {
+    const PairArgs c = pair_args(a);
+    if (int e = pair_check("sin", c)) return e;
+    if (int e = sin_check("sin", a->A, a->B, a->C, a->D)) return e;
+    return pair_launch<T>(c, sin_map<T>(a->A, a->B, a->C, a->D), stream);
+}
 
 // ----------------------------------------------------------------------------------
 // the per-image variances
@@ -188,6 +208,13 @@ int var_abrelu_impl(const VarArgs<T>& a, double h, void* stream) {
     return var_launch(a, ABReluMap<T>{T(0), T(0), (T)h, 0}, stream);
 }
 
+template <typename T>
+int var_sin_impl(const VarArgs<T>& a, double A, double B, double C, double D, void* stream) {
+    if (int e = var_check("var_sin", a)) return e;
+    if (int e = sin_check("var_sin", A, B, C, D)) return e;
+    return var_launch(a, sin_map<T>(A, B, C, D), stream);
+}
+
 // ----------------------------------------------------------------------------------
 // position-pair maps.  theta == NULL is the forward-only form.
 // ----------------------------------------------------------------------------------
@@ -205,7 +232,7 @@ struct CovArgs {
     int64_t npairs;
     int32_t h, w, same;
 };
-// of cgp_covntk_nonlin_args, cgp_abrelu_cov_args; a NULL record gives NULL fields
+// of cgp_covntk_nonlin_args, cgp_abrelu_cov_args, cgp_sin_cov_args; a NULL record gives NULL fields
 template <class A>
 CovArgs cov_args(const A* a) {
     if (!a) return CovArgs{};
@@ -308,6 +335,13 @@ int abrelu_cov_impl(const cgp_abrelu_cov_args* a, void* stream) {
         return fail(CGP_EINVAL, "abrelu_cov: s, m or hh is not finite");
     return cov_launch<T>("abrelu_cov", c, abrelu_map<T>(a->s, a->m, a->hh, a->flags), stream);
 }
+template <typename T>
+int sin_cov_impl(const cgp_sin_cov_args* a, void* stream) {
+    const CovArgs c = cov_args(a);
+    if (int e = cov_check("sin_cov", c)) return e;
+    if (int e = sin_check("sin_cov", a->A, a->B, a->C, a->D)) return e;
+    return cov_launch<T>("sin_cov", c, sin_map<T>(a->A, a->B, a->C, a->D), stream);
+}
 
 }  // namespace
 
@@ -322,6 +356,8 @@ size_t cgp_cov_nonlin_args_size(void) { return sizeof(cgp_cov_nonlin_args); }
 size_t cgp_covntk_nonlin_args_size(void) { return sizeof(cgp_covntk_nonlin_args); }
 size_t cgp_gelu_cov_args_size(void) { return sizeof(cgp_gelu_cov_args); }
 size_t cgp_abrelu_cov_args_size(void) { return sizeof(cgp_abrelu_cov_args); }
+size_t cgp_sin_args_size(void) { return sizeof(cgp_sin_args); }
+size_t cgp_sin_cov_args_size(void) { return sizeof(cgp_sin_cov_args); }
 
 #define CGP_NONLIN_ENTRY(name, impl, args)                                                \
     int name##_f64(const args* a, void* stream) { return impl<double>(a, stream); }       \
@@ -335,6 +371,8 @@ CGP_NONLIN_ENTRY(cgp_cov_nonlin, cov_nonlin_impl, cgp_cov_nonlin_args)
 CGP_NONLIN_ENTRY(cgp_covntk_nonlin, cov_nonlin_ntk_impl, cgp_covntk_nonlin_args)
 CGP_NONLIN_ENTRY(cgp_gelu_cov, gelu_cov_impl, cgp_gelu_cov_args)
 CGP_NONLIN_ENTRY(cgp_abrelu_cov, abrelu_cov_impl, cgp_abrelu_cov_args)
+CGP_NONLIN_ENTRY(cgp_sin, sin_impl, cgp_sin_args)
+CGP_NONLIN_ENTRY(cgp_sin_cov, sin_cov_impl, cgp_sin_cov_args)
 #undef CGP_NONLIN_ENTRY
 
 #define CGP_VAR_ENTRY(name, T, sfx, Map)                                                   \
@@ -359,5 +397,17 @@ int cgp_var_abrelu_f32(const float* xx, const float* yy, int64_t n1, int64_t n2,
                        int32_t same, double h, float* xx_out, float* yy_out, void* stream) {
     return var_abrelu_impl(VarArgs<float>{xx, yy, n1, n2, hw, same, xx_out, yy_out}, h, stream);
 }
+
+// the sinusoid's constants stand between `same` and the outputs
+#define CGP_VAR_SIN_ENTRY(T, sfx)                                                            \
+    int cgp_var_sin_##sfx(const T* xx, const T* yy, int64_t n1, int64_t n2, int32_t hw,      \
+                          int32_t same, double A, double B, double C, double D, T* xx_out,   \
+                          T* yy_out, void* stream) {                                         \
+        return var_sin_impl(VarArgs<T>{xx, yy, n1, n2, hw, same, xx_out, yy_out}, A, B, C,   \
+                            D, stream);                                                      \
+    }
+CGP_VAR_SIN_ENTRY(double, f64)
+CGP_VAR_SIN_ENTRY(float, f32)
+#undef CGP_VAR_SIN_ENTRY
 
 }  // extern "C"

@@ -108,6 +108,44 @@ struct ABReluMap {
     __device__ __forceinline__ T var(T v) const { return h * v; }
 };
 
+// The sinusoid φ(x) = a·sin(b·x + θ) is a function of the distance
+// d = v1 + v2 − 2c and of s = v1 + v2 + 2c: with the host's A = a²/2, B = b²/2, C = cos 2θ,
+// D = a²b²/2,
+//   K' = A·(e_d − C·e_s)     κ̇ = D·(e_d + C·e_s)     e_d = exp(−B·d), e_s = exp(−B·s)
+// and v' = A·(1 − C·exp(−4B·v)), κ̇ = D·(1 + C·exp(−4B·v)) where the ReLU overrides.  d and s
+// are raised to 0 where rounding made them negative, so e_d <= 1.  At C == 0 (Rbf: K' =
+// exp(−γ·d)) the second exponential is skipped, a launch-uniform branch; for finite inputs the
+// bits are those of the full form.  double: the library's exp; float: expf.
+__device__ __forceinline__ double exp_t(double x) { return exp(x); }
+__device__ __forceinline__ float exp_t(float x) { return expf(x); }
+
+template <typename T>
+struct SinMap {
+    T A, B, C, D;
+    // C·exp(−B·s), s raised to 0 (NaN kept)
+    __device__ __forceinline__ T ces(T s) const {
+        if (C == T(0)) return T(0);
+        s = s < T(0) ? T(0) : s;
+        return C * exp_t(-B * s);
+    }
+    template <bool NTK>
+    __device__ __forceinline__ T pair(T c, const T* vx, const T* vy, bool self, T& kdot) const {
+        const T v1 = *vx;
+        if (self) {
+            if constexpr (NTK) kdot = D * (T(1) + ces(T(4) * v1));
+            return var(v1);                                  // xy' = xx'
+        }
+        const T sum = v1 + *vy, c2 = T(2) * c;
+        T d = sum - c2;
+        d = d < T(0) ? T(0) : d;                             // NaN kept
+        const T ed = exp_t(-B * d);
+        const T ce = ces(sum + c2);
+        if constexpr (NTK) kdot = D * (ed + ce);
+        return A * (ed - ce);
+    }
+    __device__ __forceinline__ T var(T v) const { return A * (T(1) - ces(T(4) * v)); }
+};
+
 // The post-stage of the conv kernels on position-pair maps (covpool.hip, covntk.hip): the map
 // of run-time `kind` at (c, v1, v2) = (S[p, q], xx_i[p], yy_j[q]).  The override applies where
 // same, i == j and p == q.  The forward conv has no GELU post-stage (cgp_cov_conv_* rejects

@@ -656,6 +656,88 @@ int cgp_abrelu_cov_f64(const cgp_abrelu_cov_args* args, void* stream);
 int cgp_abrelu_cov_f32(const cgp_abrelu_cov_args* args, void* stream);
 
 /*
+ * The sinusoid φ(x) = a·sin(b·x + θ) (additions to ABI 12: no struct or existing entry point
+ * changed; no reference counterpart): sine and cosine networks, and with
+ * (a, b, θ) = (√2, √(2γ), π/4) the random-Fourier-feature map whose layer kernel is the
+ * squared-exponential exp(-γ·d).  In the conventions of the ReLU entry points above -- per
+ * pixel (xy, xx, yy) = (c, v1, v2), no rescaling.  For u1, u2 jointly Gaussian with zero mean,
+ * sin P·sin Q = (cos(P - Q) - cos(P + Q))/2 and E cos(g + μ) = cos μ·exp(-Var g/2) give, with
+ * four constants the caller computes in double,
+ *   A = a²/2,  B = b²/2,  C = cos 2θ,  D = a²b²/2    (each rounded once to the map's type),
+ *   d = v1 + v2 - 2c,  s = v1 + v2 + 2c,  e_d = exp(-B·d),  e_s = exp(-B·s)
+ *   pair map    out_xy = A·(e_d - C·e_s)
+ *   variances   v' = A·(1 - C·exp(-4B·v)), the pair map at c = v1 = v2 = v
+ *   NTK         out_theta = theta·κ̇,  κ̇ = D·(e_d + C·e_s) = E[φ'(u1)·φ'(u2)] = ∂out_xy/∂c
+ * d and s are raised to 0 where rounding made them negative (a NaN is kept), so e_d <= 1 and
+ * |out_xy| <= a².  Where cgp_relu_* overrides its map (same && !diag: pairs i == j; same &&
+ * diag: all), out_xy = v'[i], the same bits cgp_var_sin_* writes, and κ̇ =
+ * D·(1 + C·exp(-4B·v)).  At C == 0 the second exponential is not evaluated; for finite inputs
+ * the bits are those of the full form.  (A, B, C, D) = (1, γ, 0, 2γ) is the squared-exponential
+ * kernel: out_xy = exp(-γ·d) in (0, 1], v' = 1, κ̇ = 2γ·out_xy.  The exponential is the device
+ * math library's exp / expf; flags is ignored.  A non-finite constant, A <= 0, B <= 0 or
+ * |C| > 1 is CGP_EINVAL.
+ *
+ * cgp_sin_args has the fields and the rules of cgp_erf_args, then A, B, C, D: theta == NULL
+ * is the forward-only pass; in-place (out_xy == xy, out_theta == theta) is allowed, and theta
+ * may be xy itself; addend (optional) is added to out_xy only, as a separate rounding; same
+ * or diag need n1 == n2; hw is at most 2048; nmaps < 2^31.
+ */
+typedef struct cgp_sin_args {
+    const void* xy;         /* [nmaps][hw] */
+    const void* theta;      /* [nmaps][hw] or NULL */
+    void* out_xy;           /* [nmaps][hw] */
+    void* out_theta;        /* [nmaps][hw] (unused when theta is NULL) */
+    const void* addend;     /* [nmaps][hw] or NULL */
+    const void* xx;         /* [n1][hw] variances at the nonlinearity's input */
+    const void* yy;         /* [n2][hw] (may be NULL when same && diag) */
+    int64_t nmaps, n1, n2;
+    int32_t hw, same, diag;
+    int32_t flags;          /* ignored */
+    double A, B, C, D;      /* a²/2, b²/2, cos 2θ, a²b²/2 */
+} cgp_sin_args;
+size_t cgp_sin_args_size(void);
+int cgp_sin_f64(const cgp_sin_args* args, void* stream);
+int cgp_sin_f32(const cgp_sin_args* args, void* stream);
+/* The sinusoid on the per-image variances: xx' = A·(1 - C·exp(-4B·xx)); yy' = xx' if same
+ * else the same map of yy.  xx: [n1][hw], yy: [n2][hw].  D is checked and not used. */
+int cgp_var_sin_f64(const double* xx, const double* yy, int64_t n1, int64_t n2, int32_t hw,
+                    int32_t same, double A, double B, double C, double D, double* xx_out,
+                    double* yy_out, void* stream);
+int cgp_var_sin_f32(const float* xx, const float* yy, int64_t n1, int64_t n2, int32_t hw,
+                    int32_t same, double A, double B, double C, double D, float* xx_out,
+                    float* yy_out, void* stream);
+/*
+ * The sinusoid on position-pair maps, one entry point for both runs:
+ *   out       = map(in) [+ addend]               theta == NULL: this alone
+ *   out_theta = theta·κ̇ [+ addend_theta]         each a separate rounding
+ * with cgp_cov_nonlin_*'s element rule: (c, v1, v2) = (in[m][p, q], xx[pair_i[m]][p],
+ * yy[pair_j[m]][q]), and the override (out = v' of xx[pair_i[m]][p], κ̇ as above) where same,
+ * pair_i[m] == pair_j[m] and p == q.  theta may be in, and in-place (out == in, out_theta ==
+ * theta) is allowed: every element is read before it is written, by one thread.  out and
+ * out_theta are two buffers.  addend_theta is read only with theta.
+ */
+typedef struct cgp_sin_cov_args {
+    const void* in;            /* [npairs][h][h][w][w] */
+    const void* theta;         /* like in, or NULL: the forward-only pass */
+    void* out;
+    void* out_theta;           /* (unused when theta is NULL) */
+    const void* addend;        /* like out, or NULL */
+    const void* addend_theta;  /* like out_theta, or NULL */
+    const void* xx;            /* [n1][h][w] variances at the nonlinearity's input */
+    const void* yy;            /* [n2][h][w] (same: may be xx) */
+    const int32_t* pair_i;     /* device [npairs] */
+    const int32_t* pair_j;
+    int64_t npairs;
+    int32_t h, w;
+    int32_t same;
+    int32_t flags;             /* ignored */
+    double A, B, C, D;         /* a²/2, b²/2, cos 2θ, a²b²/2 */
+} cgp_sin_cov_args;
+size_t cgp_sin_cov_args_size(void);
+int cgp_sin_cov_f64(const cgp_sin_cov_args* args, void* stream);
+int cgp_sin_cov_f32(const cgp_sin_cov_args* args, void* stream);
+
+/*
  * out = alpha·a + beta·b (b may be NULL: out = alpha·a), n elements.  The unfused form
  * of Sum (alpha = beta = 1, kernel_patch.py:43-63) and Mixture (kernels.py:220-225).
  * Products and the sum are rounded separately (no FMA contraction), like torch.
