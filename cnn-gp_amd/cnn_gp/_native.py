@@ -195,6 +195,29 @@ class SinCovArgs(ctypes.Structure):
                                               ("D", _f64)]
 
 
+class TapConvArgs(ctypes.Structure):
+    """Mirror of cgp_tapconv_args (include/cnngp.h)."""
+    _fields_ = [
+        ("in_", _vp), ("out", _vp), ("addend", _vp), ("table", _vp),
+        ("nmaps", _i64),
+        ("h", _i32), ("w", _i32), ("ho", _i32), ("wo", _i32),
+        ("extent", _i32), ("offset", _i32), ("stride", _i32), ("dilation", _i32),
+        ("max_groups", _i32), ("reserved", _i32),
+        ("bias", _f64),
+    ]
+
+
+class TapConvCovArgs(ctypes.Structure):
+    """Mirror of cgp_tapconv_cov_args (include/cnngp.h)."""
+    _fields_ = [
+        ("in_", _vp), ("out", _vp), ("addend", _vp), ("table", _vp),
+        ("npairs", _i64),
+        ("h", _i32), ("w", _i32), ("ho", _i32), ("wo", _i32),
+        ("extent", _i32), ("offset", _i32), ("stride", _i32), ("dilation", _i32),
+        ("bias", _f64),
+    ]
+
+
 class NetOp(ctypes.Structure):
     """Mirror of cgp_net_op (include/cnngp.h)."""
     _fields_ = [
@@ -329,6 +352,12 @@ SIGNATURES = {
     "cgp_sin_cov_args_size": (ctypes.c_size_t, []),
     "cgp_sin_cov_f64": (_i32, [ctypes.POINTER(SinCovArgs), _vp]),
     "cgp_sin_cov_f32": (_i32, [ctypes.POINTER(SinCovArgs), _vp]),
+    "cgp_tapconv_args_size": (ctypes.c_size_t, []),
+    "cgp_tapconv_f64": (_i32, [ctypes.POINTER(TapConvArgs), _vp]),
+    "cgp_tapconv_f32": (_i32, [ctypes.POINTER(TapConvArgs), _vp]),
+    "cgp_tapconv_cov_args_size": (ctypes.c_size_t, []),
+    "cgp_tapconv_cov_f64": (_i32, [ctypes.POINTER(TapConvCovArgs), _vp]),
+    "cgp_tapconv_cov_f32": (_i32, [ctypes.POINTER(TapConvCovArgs), _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_axpby_f32": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_scale_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _f64, _vp]),
@@ -412,6 +441,8 @@ def load():
                 lib.cgp_sin_cov_args_size() != ctypes.sizeof(SinCovArgs) or \
                 lib.cgp_covntk_nonlin_args_size() != ctypes.sizeof(CovNonlinNtkArgs) or \
                 lib.cgp_covntk_conv_args_size() != ctypes.sizeof(CovConvNtkArgs) or \
+                lib.cgp_tapconv_args_size() != ctypes.sizeof(TapConvArgs) or \
+                lib.cgp_tapconv_cov_args_size() != ctypes.sizeof(TapConvCovArgs) or \
                 lib.cgp_net_op_size() != ctypes.sizeof(NetOp) or \
                 lib.cgp_net_args_size() != ctypes.sizeof(NetArgs) or \
                 lib.cgp_var_op_size() != ctypes.sizeof(VarOp) or \

@@ -27,7 +27,7 @@ VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
 NTK_MAPS_FUSED = True
 
 __all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "Gelu", "ABReLU", "LeakyReLU",
-           "Sin", "Cos", "Rbf",
+           "Sin", "Cos", "Rbf", "gaussian_taps",
            "GlobalAvgPool", "AvgPool2d",
            "CorrelatedConv2d", "rbf_corr", "band_corr", "Sequential", "Mixture", "Sum",
            "resnet_block")
@@ -386,7 +386,7 @@ class NNGPKernel(nn.Module):
         n2 = y.shape[0]
         plan = self._plan(h, w)
         _check_1x1(plan)
-        if not any(o.kind == "conv" for o in plan.prog.ops):
+        if not any(o.kind in ("conv", "tapconv") for o in plan.prog.ops):
             # no Conv2d, no parameters: Θ = 0 and there is no second stream to carry, so K
             # is forward's own run, bit for bit whichever path forward takes (the
             # whole-network kernel's fp64 ReLU and cgp_relu_* differ by an ulp on some pixels)
@@ -676,12 +676,37 @@ class NNGPKernel(nn.Module):
         return 0
 
 
+def gaussian_taps(k, lengthscale):
+    """The k x k table exp(-r²/(2ℓ²)) of relative tap variances, r the distance of a tap from
+    the filter's centre ((k - 1)/2 on both axes), ℓ = ``lengthscale`` > 0 in taps: a Gaussian
+    taper for ``Conv2d(..., tap_weights=...)``.  ℓ = inf is all ones, the reference's box."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"gaussian_taps: k must be a positive integer, got {k!r}")
+    try:
+        ls = float(lengthscale)
+    except (TypeError, ValueError):
+        ls = float("nan")
+    if not ls > 0:
+        raise ValueError(f"gaussian_taps: lengthscale must be positive, got {lengthscale!r}")
+    c = np.arange(int(k), dtype=np.float64) - (int(k) - 1) / 2
+    r2 = c[:, None] ** 2 + c[None, :] ** 2
+    return torch.from_numpy(np.exp(-r2 / (2.0 * ls * ls)))
+
+
 class Conv2d(NNGPKernel):
-    """kernels.py:60-98 — constant k×k kernel of value var_weight/k², plus var_bias."""
+    """kernels.py:60-98 — constant k×k kernel of value var_weight/k², plus var_bias.
+
+    As in the reference, ``kernel`` is an ordinary buffer read on every call: any finite
+    buffer of its own shape is honoured, whatever wrote it (in-place ops, ``.data =``,
+    ``load_state_dict``), as the prior variances of the conv's taps.
+    ``tap_weights``: a k×k table (tensor, array or nested list) of finite non-negative
+    relative variances W with a positive sum; the buffer is then var_weight·W/ΣW over the k×k
+    taps (the zero first row and column of an even "same" kernel are kept).  None, and a
+    table of ones, give the reference's box."""
 
     def __init__(self, kernel_size, stride=1, padding="same", dilation=1,
                  var_weight=1., var_bias=0., in_channel_multiplier=1,
-                 out_channel_multiplier=1):
+                 out_channel_multiplier=1, tap_weights=None):
         super().__init__()
         self.kernel_size = kernel_size
         self.stride = stride
@@ -703,9 +728,49 @@ class Conv2d(NNGPKernel):
         if self.kernel_has_row_of_zeros:
             kernel[:, :, 0, :] = 0.
             kernel[:, :, :, 0] = 0.
-        self.register_buffer("kernel", kernel * (self.var_weight / self.kernel_size ** 2))
+        if tap_weights is not None:
+            # W/mean(W) in double over the k x k taps (ones for a table of ones, so the
+            # product below has the box's bits), then the box's scale and dtype
+            kernel = kernel.double()
+            kernel[0, 0, side - kernel_size:, side - kernel_size:] = \
+                self._relative_taps(tap_weights, kernel_size)
+            kernel = (kernel * (self.var_weight / self.kernel_size ** 2)).to(
+                torch.get_default_dtype())
+            self.register_buffer("kernel", kernel)
+        else:
+            self.register_buffer("kernel",
+                                 kernel * (self.var_weight / self.kernel_size ** 2))
         self.in_channel_multiplier = in_channel_multiplier
         self.out_channel_multiplier = out_channel_multiplier
+
+    @staticmethod
+    def _relative_taps(tap_weights, k):
+        """``tap_weights`` as a k x k double tensor divided by its mean; ValueError naming
+        what is wrong with it."""
+        try:
+            w = torch.as_tensor(np.asarray(tap_weights.detach().cpu() if
+                                           isinstance(tap_weights, torch.Tensor)
+                                           else tap_weights, dtype=np.float64))
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"Conv2d: tap_weights is not a table of numbers ({e})") from None
+        if tuple(w.shape) != (k, k):
+            raise ValueError(f"Conv2d: tap_weights must be a {k}x{k} table for kernel_size="
+                             f"{k}, got shape {tuple(w.shape)}")
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError("Conv2d: tap_weights must be finite and non-negative, got "
+                             f"{w.tolist()}")
+        if not float(w.sum()) > 0:
+            raise ValueError("Conv2d: tap_weights must have a positive sum")
+        return w / w.mean()
+
+    def _is_box(self):
+        """The buffer is the constructor's constant box (program.conv_geometry's test)."""
+        from .program import conv_geometry
+        try:
+            conv_geometry(self)
+        except (NotImplementedError, RuntimeError):
+            return False
+        return True
 
     def layers(self):
         return 1
@@ -713,7 +778,8 @@ class Conv2d(NNGPKernel):
     def extra_repr(self):
         return (f"kernel_size={self.kernel_size}, stride={self.stride}, "
                 f"padding={self.padding}, dilation={self.dilation}, "
-                f"var_weight={self.var_weight}, var_bias={self.var_bias}")
+                f"var_weight={self.var_weight}, var_bias={self.var_bias}"
+                + ("" if self._is_box() else ", taps=custom"))
 
 
 class ReLU(NNGPKernel):

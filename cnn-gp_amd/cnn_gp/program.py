@@ -6,6 +6,8 @@ whole [N1·N2, 1, H, W] covariance tensor.  Here the tree is flattened once into
 
     v0 = moments(x, y)               kernels.py:44-49
     v  = conv(u, geometry)           kernels.py:92-98
+    v  = tapconv(u, geometry, W)     the same with a kernel buffer that is not the constant
+                                     box: its own launch on every path
     v  = relu(u)                     kernels.py:134-165
     v  = erf(u)                      Erf (no reference counterpart)
     v  = gelu(u)                     Gelu (no reference counterpart)
@@ -79,13 +81,28 @@ class CorrGeom(ConvGeom):
 
 
 @dataclasses.dataclass
+class TapGeom:
+    """A Conv2d whose kernel buffer is not the constant box: the buffer's edge
+    (k + 1 for an even "same" kernel, whose first row and column are taps like any other
+    here), offset = -padding, and the buffer itself as a tuple of tuples of float, read once
+    in double."""
+    extent: int
+    offset: int
+    stride: int
+    dilation: int
+    bias: float
+    table: tuple = ()
+
+
+@dataclasses.dataclass
 class Op:
-    # 'conv' | 'relu' | 'erf' | 'gelu' | 'abrelu' | 'sin' | 'add' | 'pool' | 'avgpool' |
-    # 'corrconv' | 'moments'
+    # 'conv' | 'tapconv' | 'relu' | 'erf' | 'gelu' | 'abrelu' | 'sin' | 'add' | 'pool' |
+    # 'avgpool' | 'corrconv' | 'moments'
     kind: str
     dst: int
     src: Optional[int] = None
-    geom: Optional[object] = None   # conv: ConvGeom, avgpool: PoolGeom, corrconv: CorrGeom
+    # conv: ConvGeom, tapconv: TapGeom, avgpool: PoolGeom, corrconv: CorrGeom
+    geom: Optional[object] = None
     shape_in: tuple = (0, 0)
     shape_out: tuple = (0, 0)
     terms: list = dataclasses.field(default_factory=list)   # add: [(coef|None, value)]
@@ -141,6 +158,25 @@ def conv_geometry(mod) -> ConvGeom:
                     bias=float(mod.var_bias))
 
 
+def tap_geometry(mod) -> TapGeom:
+    """The geometry of a Conv2d whose kernel buffer conv_geometry refuses: any finite buffer
+    of the buffer's own shape (1, 1, ke, ke), as F.conv2d reads it (kernels.py:92-97).
+    NotImplementedError naming the shape for another shape, ValueError for a non-finite
+    entry."""
+    k = int(mod.kernel_size)
+    ke = k + 1 if mod.kernel_has_row_of_zeros else k
+    if tuple(mod.kernel.shape) != (1, 1, ke, ke):
+        raise NotImplementedError(
+            f"Conv2d.kernel must keep its shape (1, 1, {ke}, {ke}) (kernel_size={k}, padding="
+            f"{mod._padding_arg!r}); got a buffer of shape {tuple(mod.kernel.shape)}")
+    kern = mod.kernel.detach().to("cpu", torch.float64).reshape(ke, ke)
+    if not bool(torch.isfinite(kern).all()):
+        raise ValueError(f"Conv2d.kernel has a non-finite entry: {kern.tolist()}")
+    return TapGeom(extent=ke, offset=-int(mod.padding), stride=int(mod.stride),
+                   dilation=int(mod.dilation), bias=float(mod.var_bias),
+                   table=tuple(tuple(float(v) for v in row) for row in kern.tolist()))
+
+
 def conv_out_hw(mod, h: int, w: int):
     """F.conv2d output size for Conv2d `mod` (kernel extent k+1 for even 'same')."""
     k, d, s, p = int(mod.kernel_size), int(mod.dilation), int(mod.stride), int(mod.padding)
@@ -192,8 +228,14 @@ def _emit(prog: Program, mod, v: int) -> int:
         h, w = prog.shapes[v]
         ho, wo = conv_out_hw(mod, h, w)
         out = prog.new_value((ho, wo))
-        prog.ops.append(Op("conv", out, src=v, geom=conv_geometry(mod), shape_in=(h, w),
-                           shape_out=(ho, wo)))
+        # the box first, by conv_geometry's own comparison (its one k x k copy to the host):
+        # a model of boxes compiles as it always did.  Any other buffer is a tapconv, which
+        # no fast path knows (fuse, NetPlan and _var_chain match "conv")
+        try:
+            kind, geom = "conv", conv_geometry(mod)
+        except NotImplementedError:
+            kind, geom = "tapconv", tap_geometry(mod)
+        prog.ops.append(Op(kind, out, src=v, geom=geom, shape_in=(h, w), shape_out=(ho, wo)))
         return out
     # one table from module class to elementwise kind (LeakyReLU is an ABReLU; Cos and Rbf
     # are Sins)
@@ -404,6 +446,8 @@ class Step:
                    replaces the geometry's: 0 on the Θ stream).  In layer_steps op is the FUSED
                    op, with its pre / post stages and their variances, and src is None where
                    the stage is the input moments (the conv reads the images)
+    fn "tapconv":  dst = A_W(src) + bias [+ addend], the conv of a kernel buffer that is not
+                   the box (op.geom: TapGeom; ``bias`` as for "conv")     cgp_tapconv_*
     fn "relu":     dst = relu(src) [+ addend], variances of value ``var``  cgp_relu_*
     fn "relu_ntk": dst, dst_theta = relu(src), theta·κ̇                   cgp_relu_ntk_*
     fn "erf":      dst = erf(src) [+ addend], variances of ``var``       cgp_erf_* (theta NULL)
@@ -436,6 +480,7 @@ class Step:
                                                                          cgp_covmap_avgpool_*
     fn "corrconv": dst = the correlated-weight conv of src (op.geom, ``bias``)
                                                                          cgp_corrconv_*
+    fn "tapconv": dst = A_W(src) + bias [+ addend] (op.geom: TapGeom)    cgp_tapconv_cov_*
     fn "axpby":   dst = Σ coef·buffer over ``terms`` (coef None: 1)      cgp_axpby_*
 
     and the two-stream list also
@@ -526,6 +571,9 @@ def layer_steps(prog: Program, pair_ops, v0: int, vf: int):
             src = None if op.pre == N.CGP_PRE_MOMENTS else K(op.src)
             steps.append(Step("conv", K(op.dst), src=src, op=op, bias=op.geom.bias,
                               addend=K(op.addend)))
+        elif op.kind == "tapconv":
+            steps.append(Step("tapconv", K(op.dst), src=K(op.src), op=op, bias=op.geom.bias,
+                              addend=K(op.addend)))
         elif op.kind in NONLIN_KINDS:
             steps.append(Step(op.kind, K(op.dst), src=K(op.src), op=op, var=op.src,
                               addend=K(op.addend)))
@@ -563,11 +611,12 @@ def ntk_steps(prog: Program, v0: int, vf: int):
     theta = {v0: None}
     for op in prog.ops:
         d, th = op.dst, theta.get(op.src)
-        if op.kind == "conv":
-            steps.append(Step("conv", ("K", d), src=("K", op.src), op=op, bias=op.geom.bias))
+        if op.kind in ("conv", "tapconv"):
+            # a tapconv is linear like the box: the same rule with its own stencil A_W
+            steps.append(Step(op.kind, ("K", d), src=("K", op.src), op=op, bias=op.geom.bias))
             theta[d] = ("K", d)
             if th is not None:
-                steps.append(Step("conv", ("T", d), src=th, op=op, bias=0.0, addend=("K", d)))
+                steps.append(Step(op.kind, ("T", d), src=th, op=op, bias=0.0, addend=("K", d)))
                 theta[d] = ("T", d)
         elif op.kind in NONLIN_KINDS:
             theta[d] = None if th is None else ("T", d)
@@ -689,7 +738,7 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
             if pooled[op.src]:
                 raise NotImplementedError(POOL_RULE_ONE)
             pooled[op.dst] = True
-        elif op.kind == "conv":
+        elif op.kind in ("conv", "tapconv"):
             if pooled[op.src] and tuple(op.shape_out) != (1, 1):
                 raise NotImplementedError(POOL_RULE_CONV)
             pooled[op.dst] = pooled[op.src]
@@ -726,6 +775,9 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
             steps.append(Step(op.kind, op.dst, src=op.src, op=op))
         elif op.kind == "corrconv":
             steps.append(Step("corrconv", op.dst, src=op.src, op=op, bias=op.geom.bias))
+        elif op.kind == "tapconv":
+            # an unfused conv: no post-nonlinearity (rule 1 matches "conv"), no addend
+            steps.append(Step("tapconv", op.dst, src=op.src, op=op, bias=op.geom.bias))
         else:
             steps.append(Step("axpby", op.dst, op=op, terms=list(op.terms)))
     bufs = [st.dst for st in steps]
@@ -867,6 +919,15 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
             if ts is not None:
                 emit(Step(st.fn, ("T", d), src=ts, op=op), shape, sc)
                 theta[d] = ("T", d)
+        elif st.fn == "tapconv":
+            # the conv's rule launch by launch: Θ' = A_W(Θ) + K' is the same entry point on Θ
+            # with bias 0 and addend K'
+            emit(Step("tapconv", K(d), src=K(st.src), op=op, bias=op.geom.bias), shape, sc)
+            theta[d] = K(d)
+            if ts is not None:
+                emit(Step("tapconv", ("T", d), src=ts, op=op, bias=0.0, addend=K(d)),
+                     shape, sc)
+                theta[d] = ("T", d)
         elif st.fn == "corrconv":
             emit(Step("corrconv", K(d), src=K(st.src), op=op, bias=op.geom.bias),
                  shape, sc)
@@ -1007,6 +1068,32 @@ class Plan:
         a.weight, a.bias = g.weight, g.bias if bias is None else bias
         return a
 
+    def _tap_table(self, op, dev, dtype):
+        """The k x k table of a tapconv op on ``dev``, rounded once to ``dtype``, uploaded once
+        per plan, device and dtype.  The copy is synchronous, as _corr_tables' is: the table
+        is shared by every stream that runs the plan, and none may see a copy in flight."""
+        cache = self.__dict__.setdefault("_tap_tabs", {})
+        key = (op.dst, str(dev), dtype)
+        tab = cache.get(key)
+        if tab is None:
+            tab = torch.tensor(op.geom.table, dtype=torch.float64).to(dtype).to(dev).contiguous()
+            torch.cuda.synchronize(dev)
+            cache[key] = tab
+        return tab
+
+    def _tapconv_launch(self, op, sfx, stream, src, out, nmaps, bias, addend=None):
+        """One cgp_tapconv_* launch of tapconv ``op`` over ``nmaps`` maps."""
+        g = op.geom
+        a = N.TapConvArgs()
+        a.in_, a.out, a.nmaps = src.data_ptr(), out.data_ptr(), nmaps
+        if addend is not None:
+            a.addend = addend.data_ptr()
+        a.table = self._tap_table(op, out.device, out.dtype).data_ptr()
+        (a.h, a.w), (a.ho, a.wo) = op.shape_in, op.shape_out
+        a.extent, a.offset, a.stride, a.dilation = g.extent, g.offset, g.stride, g.dilation
+        a.bias = bias
+        N.check(getattr(N.load(), f"cgp_tapconv_{sfx}")(a, stream), "cgp_tapconv")
+
     def _last_use(self, ops, extra_final):
         last = {}
         for idx, o in enumerate(ops):
@@ -1051,6 +1138,16 @@ class Plan:
                 for src, dst, n in parts:
                     a = self._conv_args(op, src, dst, n, n, 1)
                     N.check(getattr(N.load(), f"cgp_conv_{sfx}")(a, stream), "cgp_conv")
+                out = (buf[:n1], buf[n1:])
+            elif op.kind == "tapconv":
+                # the same entry point over the [n1 + n2] variance maps (a pure map op)
+                xin, yin = vals[op.src]
+                buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
+                parts = ((xin, buf[:n1], n1), (yin, buf[n1:], n2))
+                if _adjacent(xin, yin):
+                    parts = ((xin, buf, n1 + n2),)
+                for src, dst, n in parts:
+                    self._tapconv_launch(op, sfx, stream, src, dst, n, op.geom.bias)
                 out = (buf[:n1], buf[n1:])
             elif op.kind in NONLIN_KINDS:
                 xin, yin = vals[op.src]
@@ -1269,6 +1366,9 @@ class Plan:
                 a = self._conv_args(op, bufs.get(st.src), out, nmaps, n1, n2, same, diag,
                                     self.flags, st.bias, bufs.get(st.addend), var, (x, y))
                 N.check(conv(a, stream), "cgp_conv")
+            elif st.fn == "tapconv":
+                self._tapconv_launch(op, sfx, stream, bufs[st.src], out, nmaps, st.bias,
+                                     bufs.get(st.addend))
             elif st.fn == "axpby":
                 _axpby_terms(sfx, [(c, bufs[b]) for c, b in st.terms], out, out.numel(), stream)
             else:
@@ -1470,6 +1570,15 @@ class Plan:
                         r = stencil(maps(N.CorrConvArgs(), st), st)
                         rr, rc = self._corr_tables(st.op, dev, x.dtype)
                         r.corr_rows, r.corr_cols = N.ptr(rr), N.ptr(rc)
+                    elif st.fn == "tapconv":
+                        what = "cgp_tapconv_cov"
+                        r = maps(N.TapConvCovArgs(), st)
+                        g = st.op.geom
+                        r.ho, r.wo = h, w
+                        r.extent, r.offset, r.stride, r.dilation = \
+                            g.extent, g.offset, g.stride, g.dilation
+                        r.bias, r.addend = st.bias, ptr[st.addend]
+                        r.table = N.ptr(self._tap_table(st.op, dev, x.dtype))
                     else:
                         raise AssertionError(st.fn)
                     N.check(getattr(lib, f"{what}_{sfx}")(r, stream), what)

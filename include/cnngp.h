@@ -422,6 +422,77 @@ int cgp_corrconv_f64(const cgp_corrconv_args* args, void* stream);
 int cgp_corrconv_f32(const cgp_corrconv_args* args, void* stream);
 
 /*
+ * A conv whose taps carry individual weights (additions to ABI 12: no struct or existing
+ * entry point changed).  Conv2d.propagate of the reference is F.conv2d with the
+ * module's `kernel` buffer (kernels.py:92-98); these entry points run it for a buffer that is
+ * not the constant box of cgp_conv_*.  A pure map op, with no n1 / n2 / same / diag:
+ *   out[m][oh][ow] = ( Σ_{a<extent} p_a ) + bias  [+ addend[m][oh][ow]]
+ *   p_a            =   Σ_{b<extent} table[a][b] · in[m][oh·s + off + a·d][ow·s + off + b·d]
+ * with a term zero where an index leaves the h×w map.  `extent` is the buffer's edge (k + 1
+ * for an even "same" kernel) and `offset` is -padding: the first row and column of an even
+ * "same" buffer are taps like any other.  The arithmetic, all in the maps' type:
+ *   - table is given in the maps' type (the caller rounds it once);
+ *   - every product is rounded (the library is built with -ffp-contract=off);
+ *   - p_a accumulates its products left to right, b = 0, 1, ...;
+ *   - the p_a are added top to bottom, a = 0, 1, ..., then bias; the addend is added last,
+ *     a separate rounding;
+ *   - a tap whose weight is exactly zero may be skipped (the zero row and column of an even
+ *     "same" kernel cost nothing); for finite inputs that changes no value.
+ * The order depends on the geometry alone, not on the grid, nmaps or the maps a workgroup
+ * takes: where a map has fewer than 64 outputs the tap rows a of one output are split over
+ * the lanes of a wave, each p_a still summed by one lane, and the p_a are then added top to
+ * bottom by one lane -- the same bits as one lane doing all of it.
+ * out must not be in (out == addend is allowed).  ho, wo must be F.conv2d's,
+ *   ho = floor((h - 2·offset - d·(extent - 1) - 1)/s) + 1, wo likewise,
+ * and every output row and column must have a tap inside the map.  LDS budget: a workgroup
+ * stages whole maps with the zero border the taps reach, [(ho-1)·s + (extent-1)·d + 1] x
+ * [(wo-1)·s + (extent-1)·d + 1] elements; one such map, plus extent p_a per output where the
+ * rows are split, must fit 64 KB (32×32 maps with 7×7 taps and a 28×28 readout do, in either
+ * type).  Every check returns CGP_EINVAL before any launch.
+ */
+typedef struct cgp_tapconv_args {
+    const void* in;          /* [nmaps][h][w] */
+    void* out;               /* [nmaps][ho][wo] */
+    const void* addend;      /* like out, or NULL */
+    const void* table;       /* device [extent][extent], the maps' type */
+    int64_t nmaps;
+    int32_t h, w, ho, wo;
+    int32_t extent, offset, stride, dilation;
+    int32_t max_groups;      /* as cgp_conv_args.max_groups: 0 = the library's grid, > 0 caps
+                                it (each workgroup walks more chunks; no result bit changes),
+                                < 0: CGP_EINVAL */
+    int32_t reserved;
+    double bias;
+} cgp_tapconv_args;
+size_t cgp_tapconv_args_size(void);
+int cgp_tapconv_f64(const cgp_tapconv_args* args, void* stream);
+int cgp_tapconv_f32(const cgp_tapconv_args* args, void* stream);
+/*
+ * The same conv on position-pair maps, in the layout and with the pair conventions of
+ * cgp_cov_conv_*: p and q move by the same tap,
+ *   out[m][P][Q][U][V] = ( Σ_a p_a ) + bias [+ addend]
+ *   p_a = Σ_b table[a][b] · in[m][P·s+off+a·d][Q·s+off+a·d][U·s+off+b·d][V·s+off+b·d]
+ * in the order above, so the P = Q, U = V entries of a self pair's map equal cgp_tapconv_* on
+ * the image's variance map bit for bit.  No post-nonlinearity, no pair lists: nothing reads
+ * variances.  out must not be in (out == addend is allowed).  One workgroup stages `extent`
+ * w×w blocks: extent·w²·itemsize, and 8 bytes per tap row, must not exceed 64 KB.  A 1×1
+ * value is a map of one element.
+ */
+typedef struct cgp_tapconv_cov_args {
+    const void* in;          /* [npairs][h][h][w][w] */
+    void* out;               /* [npairs][ho][ho][wo][wo] */
+    const void* addend;      /* like out, or NULL */
+    const void* table;       /* device [extent][extent], the maps' type */
+    int64_t npairs;
+    int32_t h, w, ho, wo;
+    int32_t extent, offset, stride, dilation;
+    double bias;
+} cgp_tapconv_cov_args;
+size_t cgp_tapconv_cov_args_size(void);
+int cgp_tapconv_cov_f64(const cgp_tapconv_cov_args* args, void* stream);
+int cgp_tapconv_cov_f32(const cgp_tapconv_cov_args* args, void* stream);
+
+/*
  * The GELU nonlinearity φ(x) = x·Φ(x) (additions to ABI 12: no struct or existing entry
  * point changed; no reference counterpart).  The exact GELU, not its tanh
  * approximation.  Its layer kernel in closed form (Tsuchida, Pearce et al. 2021, "Avoiding
