@@ -195,6 +195,36 @@ class SinCovArgs(ctypes.Structure):
                                               ("D", _f64)]
 
 
+_HERMITE_TABLES = [("ax", _vp), ("ay", _vp), ("dax", _vp), ("day", _vp),
+                   ("stride_x", _i64), ("stride_y", _i64), ("order", _i32), ("reserved", _i32)]
+
+# cgp_hermite_*'s function ids (CGP_HERMITE_*), by the name HermiteNonlin takes
+HERMITE_PHI = {"tanh": 0, "sigmoid": 1, "softplus": 2, "silu": 3, "gelu_tanh": 4, "erf": 5,
+               "gelu": 6}
+CGP_HERMITE_MAX_ORDER = 64
+CGP_HERMITE_MAX_NODES = 256
+
+
+class HermiteCoefArgs(ctypes.Structure):
+    """Mirror of cgp_hermite_coef_args (include/cnngp.h)."""
+    _fields_ = [
+        ("var", _vp), ("a", _vp), ("da", _vp), ("nodes", _vp),
+        ("count", _i64),
+        ("phi", _i32), ("order", _i32), ("nq", _i32), ("flags", _i32),
+    ]
+
+
+class HermiteArgs(ctypes.Structure):
+    """Mirror of cgp_hermite_args (include/cnngp.h): cgp_erf_args' fields, then the tables."""
+    _fields_ = list(ErfArgs._fields_) + _HERMITE_TABLES
+
+
+class HermiteCovArgs(ctypes.Structure):
+    """Mirror of cgp_hermite_cov_args (include/cnngp.h): cgp_abrelu_cov_args' maps, then the
+    tables."""
+    _fields_ = ABReluCovArgs._fields_[:-3] + _HERMITE_TABLES
+
+
 class TapConvArgs(ctypes.Structure):
     """Mirror of cgp_tapconv_args (include/cnngp.h)."""
     _fields_ = [
@@ -358,6 +388,19 @@ SIGNATURES = {
     "cgp_tapconv_cov_args_size": (ctypes.c_size_t, []),
     "cgp_tapconv_cov_f64": (_i32, [ctypes.POINTER(TapConvCovArgs), _vp]),
     "cgp_tapconv_cov_f32": (_i32, [ctypes.POINTER(TapConvCovArgs), _vp]),
+    "cgp_hermite_coef_args_size": (ctypes.c_size_t, []),
+    "cgp_hermite_coef_f64": (_i32, [ctypes.POINTER(HermiteCoefArgs), _vp]),
+    "cgp_hermite_coef_f32": (_i32, [ctypes.POINTER(HermiteCoefArgs), _vp]),
+    "cgp_hermite_args_size": (ctypes.c_size_t, []),
+    "cgp_hermite_f64": (_i32, [ctypes.POINTER(HermiteArgs), _vp]),
+    "cgp_hermite_f32": (_i32, [ctypes.POINTER(HermiteArgs), _vp]),
+    "cgp_var_hermite_f64": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp,
+                                   _vp, _vp, _vp]),
+    "cgp_var_hermite_f32": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp,
+                                   _vp, _vp, _vp]),
+    "cgp_hermite_cov_args_size": (ctypes.c_size_t, []),
+    "cgp_hermite_cov_f64": (_i32, [ctypes.POINTER(HermiteCovArgs), _vp]),
+    "cgp_hermite_cov_f32": (_i32, [ctypes.POINTER(HermiteCovArgs), _vp]),
     "cgp_axpby_f64": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_axpby_f32": (_i32, [_f64, _vp, _f64, _vp, _vp, _i64, _vp]),
     "cgp_scale_batch_f64": (_i32, [_i32, _vp, _vp, _vp, _f64, _vp]),
@@ -439,6 +482,9 @@ def load():
                 lib.cgp_abrelu_cov_args_size() != ctypes.sizeof(ABReluCovArgs) or \
                 lib.cgp_sin_args_size() != ctypes.sizeof(SinArgs) or \
                 lib.cgp_sin_cov_args_size() != ctypes.sizeof(SinCovArgs) or \
+                lib.cgp_hermite_coef_args_size() != ctypes.sizeof(HermiteCoefArgs) or \
+                lib.cgp_hermite_args_size() != ctypes.sizeof(HermiteArgs) or \
+                lib.cgp_hermite_cov_args_size() != ctypes.sizeof(HermiteCovArgs) or \
                 lib.cgp_covntk_nonlin_args_size() != ctypes.sizeof(CovNonlinNtkArgs) or \
                 lib.cgp_covntk_conv_args_size() != ctypes.sizeof(CovConvNtkArgs) or \
                 lib.cgp_tapconv_args_size() != ctypes.sizeof(TapConvArgs) or \

@@ -27,7 +27,8 @@ VAR_CHAIN = os.environ.get("CGP_VAR_CHAIN", "1") != "0"
 NTK_MAPS_FUSED = True
 
 __all__ = ("NNGPKernel", "Conv2d", "ReLU", "Erf", "Gelu", "ABReLU", "LeakyReLU",
-           "Sin", "Cos", "Rbf", "gaussian_taps",
+           "Sin", "Cos", "Rbf",
+           "HermiteNonlin", "Tanh", "Sigmoid", "Softplus", "SiLU", "GeluTanh", "gaussian_taps",
            "GlobalAvgPool", "AvgPool2d",
            "CorrelatedConv2d", "rbf_corr", "band_corr", "Sequential", "Mixture", "Sum",
            "resnet_block")
@@ -204,6 +205,9 @@ class NNGPKernel(nn.Module):
             elif isinstance(m, Sin):
                 # the constants are in the op records: a plan serves one (A, B, C, D)
                 key.append(("sin", *m.constants()))
+            elif isinstance(m, HermiteNonlin):
+                # the rule is in the op records: a plan serves one (phi, order, quad_nodes)
+                key.append(("hermite", *m.rule()))
             elif isinstance(m, Mixture):
                 mixture = True
                 key.append(("m", tuple(m.proportions())))
@@ -259,7 +263,8 @@ class NNGPKernel(nn.Module):
         """Evaluate the ReLU map op by op exactly like the reference (correctly rounded
         1/sqrt, sqrt, acos, division) instead of the closed form (default; within 1e-14 of
         the exact map, see csrc/relu_poly.h).  For parity studies; ~2x slower.  An Erf and
-        a Gelu have one evaluation mode and ignore it, and so does a Sin / Cos / Rbf; an ABReLU / LeakyReLU evaluates the
+        a Gelu have one evaluation mode and ignore it, and so do a Sin / Cos / Rbf and a
+        HermiteNonlin; an ABReLU / LeakyReLU evaluates the
         ReLU map inside it in the chosen mode."""
         for m in self.modules():
             m.__dict__["_cgp_exact_relu"] = bool(enabled)
@@ -359,6 +364,8 @@ class NNGPKernel(nn.Module):
                             e_d = exp(−B·(v₁ + v₂ − 2c)), e_s = exp(−B·(v₁ + v₂ + 2c)) and
                             (B, C, D) = (b²/2, cos 2θ, a²b²/2); κ̇ = D·(1 + C·exp(−4B·v)) where
                             K' is overridden; Cos is θ = π/2, Rbf(γ) is κ̇ = 2γ·K'  
+            HermiteNonlin   K' as forward,         Θ' = Θ·κ̇,  κ̇ = Σ a'_n(v₁)·a'_n(v₂)·ρⁿ, the
+                            series of φ' (Tanh, Sigmoid, Softplus, SiLU, GeluTanh)
             Sum / Mixture   the same (weighted) sum on both
 
         and the result is Θ of the final 1x1 value; a model without a Conv2d gives zeros
@@ -503,7 +510,8 @@ class NNGPKernel(nn.Module):
         """The neural tangent kernel Θ, [N1, N2] (or [N1] when diag), carried on position-pair
         maps; with ``return_nngp`` the pair (K, Θ).  Valid for every model forward runs on
         position-pair maps -- a GlobalAvgPool, AvgPool2d or CorrelatedConv2d anywhere the
-        forward rules allow, with ReLU, Erf, Gelu, ABReLU and Sin / Cos / Rbf -- and for a model
+        forward rules allow, with ReLU, Erf, Gelu, ABReLU, Sin / Cos / Rbf and HermiteNonlin -- and
+        for a model
         with none of them,
         where it is a second, slower route to ``ntk``'s result.
 
@@ -936,6 +944,103 @@ class Rbf(Sin):
 
     def extra_repr(self):
         return f"gamma={self.gamma}"
+
+
+class HermiteNonlin(NNGPKernel):
+    """Any smooth φ by its Hermite (Mehler) series (no reference counterpart):
+    ``phi`` is one of "tanh", "sigmoid", "softplus", "silu", "gelu_tanh" (GELU's tanh
+    approximation), and "erf" and "gelu" (the exact x·Φ(x)), which exist so that this path can
+    be checked against Erf() and Gelu().  With ρ = c/√(v₁·v₂) and a_n(v) = E_z[φ(√v·z)·h_n(z)],
+    h_n = He_n/√n!,
+    K' = Σ_{n<=order} a_n(v₁)·a_n(v₂)·ρⁿ,  κ̇ = the same of φ',  v' = Σ a_n(v)²,
+    the coefficients from a Gauss–Hermite rule of ``quad_nodes`` nodes, compressed to |z| <= 12.5
+    (program.hermite_rule), per image pixel (device: hermite_coef_kernel, HermiteMap).  The truncated series is symmetric bit for bit and
+    positive semi-definite by construction; its error is the dropped tail, largest at |ρ| = 1
+    and growing with the variance for a saturating φ (2e-7 of E φ² for tanh at v = 1 and order
+    32, 2e-4 at v = 4).  Usable wherever Sin is: forward, ntk, position_covariance, the pooled
+    path and ntk_maps; a model with one runs on the layer path, and set_exact_relu has no effect
+    on it.  ``phi``, ``order`` and ``quad_nodes`` are plain attributes: assigning one takes
+    effect at the next call."""
+
+    def __init__(self, phi, order=32, quad_nodes=96):
+        super().__init__()
+        self.phi = phi
+        self.order = order
+        self.quad_nodes = quad_nodes
+        self.rule()
+
+    def rule(self):
+        """(function id, order, quad_nodes) as the kernels take them, validated."""
+        name = type(self).__name__
+        phi, order, nq = self.phi, self.order, self.quad_nodes
+        if phi not in N.HERMITE_PHI:
+            raise ValueError(f"{name}: phi must be one of {sorted(N.HERMITE_PHI)}, got {phi!r}")
+        for what, val in (("order", order), ("quad_nodes", nq)):
+            if isinstance(val, bool) or not isinstance(val, int):
+                raise ValueError(f"{name}: {what} must be an int, got {val!r}")
+        if not 1 <= order <= N.CGP_HERMITE_MAX_ORDER:
+            raise ValueError(f"{name}: order must be in [1, {N.CGP_HERMITE_MAX_ORDER}], "
+                             f"got {order}")
+        if not order < nq <= N.CGP_HERMITE_MAX_NODES:
+            raise ValueError(f"{name}: quad_nodes must be above order = {order} and at most "
+                             f"{N.CGP_HERMITE_MAX_NODES}, got {nq}")
+        return N.HERMITE_PHI[phi], order, nq
+
+    def layers(self):
+        return 0
+
+    def extra_repr(self):
+        return f"phi={self.phi!r}, order={self.order}, quad_nodes={self.quad_nodes}"
+
+
+class Tanh(HermiteNonlin):
+    """φ(x) = tanh x: HermiteNonlin("tanh")."""
+
+    def __init__(self, order=32, quad_nodes=96):
+        super().__init__("tanh", order, quad_nodes)
+
+    def extra_repr(self):
+        return f"order={self.order}, quad_nodes={self.quad_nodes}"
+
+
+class Sigmoid(HermiteNonlin):
+    """φ(x) = 1/(1 + exp(−x)): HermiteNonlin("sigmoid")."""
+
+    def __init__(self, order=32, quad_nodes=96):
+        super().__init__("sigmoid", order, quad_nodes)
+
+    def extra_repr(self):
+        return f"order={self.order}, quad_nodes={self.quad_nodes}"
+
+
+class Softplus(HermiteNonlin):
+    """φ(x) = log(1 + exp x): HermiteNonlin("softplus")."""
+
+    def __init__(self, order=32, quad_nodes=96):
+        super().__init__("softplus", order, quad_nodes)
+
+    def extra_repr(self):
+        return f"order={self.order}, quad_nodes={self.quad_nodes}"
+
+
+class SiLU(HermiteNonlin):
+    """φ(x) = x/(1 + exp(−x)), the swish: HermiteNonlin("silu")."""
+
+    def __init__(self, order=32, quad_nodes=96):
+        super().__init__("silu", order, quad_nodes)
+
+    def extra_repr(self):
+        return f"order={self.order}, quad_nodes={self.quad_nodes}"
+
+
+class GeluTanh(HermiteNonlin):
+    """φ(x) = x·(1 + tanh(√(2/π)·(x + 0.044715·x³)))/2, GELU's tanh approximation: HermiteNonlin("gelu_tanh")."""
+
+    def __init__(self, order=32, quad_nodes=96):
+        super().__init__("gelu_tanh", order, quad_nodes)
+
+    def extra_repr(self):
+        return f"order={self.order}, quad_nodes={self.quad_nodes}"
 
 
 class GlobalAvgPool(NNGPKernel):

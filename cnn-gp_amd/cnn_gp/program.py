@@ -13,6 +13,8 @@ whole [N1·N2, 1, H, W] covariance tensor.  Here the tree is flattened once into
     v  = gelu(u)                     Gelu (no reference counterpart)
     v  = abrelu(u; a, b)             ABReLU / LeakyReLU (no reference counterpart)
     v  = sin(u; A, B, C, D)          Sin / Cos / Rbf (no reference counterpart)
+    v  = hermite(u; phi, N, Q)       HermiteNonlin: Tanh, Sigmoid, Softplus, SiLU, GeluTanh (no
+                                     reference counterpart)
     v  = add[(coef, u), ...]         Sum (kernels.py:252-254) / Mixture (:220-225)
     v  = pool(u)                     GlobalAvgPool (no reference counterpart; DESIGN §3.3:
                                      such a program runs on position-pair maps, pool_steps)
@@ -44,8 +46,10 @@ position-pair maps, in Plan.run_cov_steps.
 from __future__ import annotations
 
 import dataclasses
+import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -96,8 +100,8 @@ class TapGeom:
 
 @dataclasses.dataclass
 class Op:
-    # 'conv' | 'tapconv' | 'relu' | 'erf' | 'gelu' | 'abrelu' | 'sin' | 'add' | 'pool' |
-    # 'avgpool' | 'corrconv' | 'moments'
+    # 'conv' | 'tapconv' | 'relu' | 'erf' | 'gelu' | 'abrelu' | 'sin' | 'hermite' | 'add' |
+    # 'pool' | 'avgpool' | 'corrconv' | 'moments'
     kind: str
     dst: int
     src: Optional[int] = None
@@ -118,6 +122,8 @@ class Op:
     smh: Optional[tuple] = None
     # sin: the kernels' constants (A, B, C, D) = (a²/2, b²/2, cos 2θ, a²b²/2), computed in double
     consts: Optional[tuple] = None
+    # hermite: (function id, order, quad_nodes) of the series (HermiteNonlin.rule)
+    rule: Optional[tuple] = None
 
 
 class Program:
@@ -240,12 +246,14 @@ def _emit(prog: Program, mod, v: int) -> int:
     # one table from module class to elementwise kind (LeakyReLU is an ABReLU; Cos and Rbf
     # are Sins)
     kind = next((k for cls, k in ((K.ReLU, "relu"), (K.Erf, "erf"), (K.Gelu, "gelu"),
-                                  (K.ABReLU, "abrelu"), (K.Sin, "sin"))
+                                  (K.ABReLU, "abrelu"), (K.Sin, "sin"),
+                                  (K.HermiteNonlin, "hermite"))
                  if isinstance(mod, cls)), None)
     if kind is not None:
         out = prog.new_value(prog.shapes[v])
         consts = dict(slopes=(float(mod.a), float(mod.b)), smh=mod.constants()) \
-            if kind == "abrelu" else dict(consts=mod.constants()) if kind == "sin" else {}
+            if kind == "abrelu" else dict(consts=mod.constants()) if kind == "sin" else \
+            dict(rule=mod.rule()) if kind == "hermite" else {}
         prog.ops.append(Op(kind, out, src=v, shape_in=prog.shapes[v], shape_out=prog.shapes[v],
                            **consts))
         return out
@@ -398,7 +406,7 @@ def fuse(prog: Program, v0: int, vf: int, enable: bool = True, pre_relu: bool = 
 
 
 # the op kinds that read the per-image variances of their source
-NONLIN_KINDS = ("relu", "erf", "gelu", "abrelu", "sin")
+NONLIN_KINDS = ("relu", "erf", "gelu", "abrelu", "sin", "hermite")
 
 # The layer-path entry point cgp_<name>_* of every nonlinearity: its argument class, that
 # class's K' output field, whether the record takes the ReLU evaluation flags, the record's
@@ -414,6 +422,9 @@ NONLIN_CALLS = {
                lambda op: (op.smh[2],)),
     "sin": (N.SinArgs, "out_xy", False, lambda op: zip("ABCD", op.consts),
             lambda op: op.consts),
+    # the record's tables and cgp_var_hermite_*'s node table live on a device: Plan fills them
+    # in (_hermite_tables, _hermite_nodes)
+    "hermite": (N.HermiteArgs, "out_xy", False, None, lambda op: op.rule),
 }
 
 
@@ -460,6 +471,11 @@ class Step:
     fn "sin":      dst = sin(src; op.consts) [+ addend], variances of ``var``
                                                                          cgp_sin_* (theta NULL)
     fn "sin_ntk":  dst, dst_theta = sin(src), theta·κ̇                    cgp_sin_*
+    fn "hermite":  dst = hermite(src; op.rule) [+ addend], variances of ``var``: the
+                   coefficient tables of ``var`` (cgp_hermite_coef_*), then
+                                                                         cgp_hermite_* (theta NULL)
+    fn "hermite_ntk": dst, dst_theta = hermite(src), theta·κ̇: the tables of φ and φ', then
+                                                                         cgp_hermite_*
     fn "axpby":    dst = Σ coef·buffer over ``terms`` (coef None: 1)     cgp_axpby_*
 
     Either list on position-pair maps may hold
@@ -475,6 +491,9 @@ class Step:
                                                                          cgp_abrelu_cov_*
     fn "sin":     dst = sin of src (op.consts), variances of value ``var`` [+ addend]
                                                                          cgp_sin_cov_*
+    fn "hermite": dst = hermite of src (op.rule), variances of value ``var`` [+ addend]: the
+                  coefficient tables of ``var`` (cgp_hermite_coef_*), then
+                                                                         cgp_hermite_cov_*
     fn "pool":    dst = mean over (p, q) of src                          cgp_cov_pool_*
     fn "avgpool": dst = mean of src over the windows of p and of q (op.geom)
                                                                          cgp_covmap_avgpool_*
@@ -493,6 +512,8 @@ class Step:
                                                                           cgp_abrelu_cov_*
     fn "sin_ntk":    dst, dst_theta = sin of src [+ addend], theta·κ̇ [+ addend_theta]
                                                                           cgp_sin_cov_*
+    fn "hermite_ntk": dst, dst_theta = hermite of src [+ addend], theta·κ̇ [+ addend_theta]: the
+                     tables of φ and φ', then                             cgp_hermite_cov_*
     fn "accum":      dst = dst + src, in place                            cgp_axpby_*"""
     fn: str
     dst: object
@@ -601,6 +622,7 @@ def ntk_steps(prog: Program, v0: int, vf: int):
         Gelu            K' = gelu(K),          Θ' = Θ·κ̇,  κ̇ = E[φ'φ']   
         ABReLU          K' = abrelu(K),        Θ' = Θ·κ̇,  κ̇ = s·(π - θ)/2π + m  
         Sin             K' = sin(K),           Θ' = Θ·κ̇,  κ̇ = D·(e_d + C·e_s)   
+        HermiteNonlin   K' = hermite(K),       Θ' = Θ·κ̇,  κ̇ = the series of φ'  
         Sum / Mixture   the same (weighted) sum on both streams
 
     A zero Θ is carried as None and costs nothing: the first conv's Θ' IS its K' (the same
@@ -659,6 +681,9 @@ ABRELU_RULE_GLOBAL = ("an ABReLU / LeakyReLU downstream of a GlobalAvgPool is no
                       "it would need the pooled self-covariances of each image (DESIGN §8)")
 SIN_RULE_GLOBAL = ("a Sin / Cos / Rbf downstream of a GlobalAvgPool is not implemented: it would "
                    "need the pooled self-covariances of each image (DESIGN §8)")
+HERMITE_RULE_GLOBAL = ("a HermiteNonlin (Tanh, Sigmoid, Softplus, SiLU, GeluTanh) downstream of a "
+                       "GlobalAvgPool is not implemented: it would need the pooled "
+                       "self-covariances of each image (DESIGN §8)")
 CORRCONV_RULE_NTK = ("ntk: the neural tangent kernel of a model with a CorrelatedConv2d is not "
                      "implemented: Θ would have to be carried as position-pair maps (DESIGN §8)")
 
@@ -701,6 +726,7 @@ class CovSteps:
 # op kind -> the rule it breaks downstream of a GlobalAvgPool (its result is not pooled)
 POOL_RULES = {"relu": POOL_RULE_NONLIN, "erf": POOL_RULE_NONLIN, "gelu": GELU_RULE_GLOBAL,
               "abrelu": ABRELU_RULE_GLOBAL, "sin": SIN_RULE_GLOBAL,
+              "hermite": HERMITE_RULE_GLOBAL,
               "avgpool": AVGPOOL_RULE_GLOBAL, "corrconv": CORRCONV_RULE_GLOBAL}
 
 
@@ -768,7 +794,7 @@ def pool_steps(prog: Program, v0: int, vf: int, body: bool = False) -> CovSteps:
             steps.append(Step("nonlin", op.dst, src=op.src, op=op,
                                  post=N.CGP_COV_RELU if op.kind == "relu" else N.CGP_COV_ERF,
                                  var=op.src, addend=op.addend))
-        elif op.kind in ("gelu", "abrelu", "sin"):
+        elif op.kind in ("gelu", "abrelu", "sin", "hermite"):
             steps.append(Step(op.kind, op.dst, src=op.src, op=op, var=op.src,
                                  addend=op.addend))
         elif op.kind in ("pool", "avgpool"):
@@ -818,8 +844,9 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
         Conv2d, CorrelatedConv2d   K' = A(K) + b,   Θ' = A(Θ) + K'   (correlated weights are a
                                    fixed linear map of i.i.d. parameters: the conv's rule, A_R)
         ReLU / Erf / Gelu          K' as forward,   Θ' = Θ·κ̇
-        ABReLU, Sin                K' as forward,   Θ' = Θ·κ̇   (cgp_abrelu_cov_* / cgp_sin_cov_*
-                                   with theta: a launch of its own, never a conv's post-stage)
+        ABReLU, Sin, HermiteNonlin K' as forward,   Θ' = Θ·κ̇   (cgp_abrelu_cov_* / cgp_sin_cov_* /
+                                   cgp_hermite_cov_* with theta: a launch of its own, never a
+                                   conv's post-stage)
         AvgPool2d, GlobalAvgPool   the same linear op on both
         Sum / Mixture              the same (weighted) sum on both
 
@@ -903,7 +930,7 @@ def pool_ntk_steps(prog: Program, v0: int, vf: int, body: bool = False, fused: b
                              var=st.var, addend=ka, theta=ts, dst_theta=("T", d),
                              addend_theta=ta), shape, sc)
                 theta[d] = ("T", d)
-        elif st.fn in ("abrelu", "sin"):
+        elif st.fn in ("abrelu", "sin", "hermite"):
             # a launch of its own on either run: one entry point, with and without Θ
             if ts is None:
                 emit(Step(st.fn, K(d), src=K(st.src), op=op, var=st.var, addend=ka),
@@ -973,6 +1000,27 @@ def _axpby_terms(sfx, terms, out, n, stream):
             N.call(f"cgp_axpby_{sfx}", 1.0, N.ptr(out), c, N.ptr(src), N.ptr(out), n, stream)
 
 
+# Plan._hermite_nodes' tables, per (device, quad_nodes)
+_HERMITE_NODES = {}
+# where the compressed Gauss–Hermite rule ends: h_n(z)·exp(−z²/2) is below exp(−z²/4) for every
+# n, 1e-17 at |z| = 12.5
+HERMITE_RANGE = 12.5
+
+
+def hermite_rule(nq):
+    """(z, w), float64 [nq] each: the nodes and weights of the rule E_z[f(z)] = Σ w_q·f(z_q)
+    behind the Hermite coefficients.  numpy's hermegauss(nq), weights over
+    √(2π), compressed by s = min(1, HERMITE_RANGE / max|z_q|): z = s·z_q, w = s·w_q·exp((1 −
+    s²)·z_q²/2), the same integral after the substitution z → s·z.  The plain rule spends its
+    outer nodes where every integrand is below rounding; pulled in to ±12.5 they sit closer
+    together, which is what a φ with poles near the real axis (tanh: ±iπ/2) needs: at 96 nodes
+    and v = 1 the coefficients of tanh go from 4.6e-10 to the rounding level.  s is 1 up to 46
+    nodes."""
+    z, w = np.polynomial.hermite_e.hermegauss(int(nq))
+    s = min(1.0, HERMITE_RANGE / float(np.max(np.abs(z))))
+    return s * z, s * w * np.exp((1 - s * s) * z * z / 2) / math.sqrt(2 * math.pi)
+
+
 class DevPtr:
     """A device address inside ``base`` (kept alive by the handle, like a view would be):
     what the launch records need of a variance map, without building a tensor view."""
@@ -1033,9 +1081,53 @@ class Plan:
         r.hw, r.same, r.diag = ho * wo, int(same), int(diag)
         for field, value in consts(op) if consts else ():
             setattr(r, field, value)
+        if op.kind == "hermite":
+            ws = self._hermite_tables(  # noqa: F841 (alive until the launch)
+                r, op, sfx, stream, vx, vy, n1, n2, ho * wo, same, theta is not None, out)
         if has_flags:
             r.flags = self.flags
         N.check(getattr(N.load(), f"cgp_{name}_{sfx}")(r, stream), "cgp_" + name)
+
+    @staticmethod
+    def _hermite_nodes(dev, nq):
+        """The device node table of cgp_hermite_coef_* / cgp_var_hermite_*: double [2][nq], the
+        nodes and the weights of hermite_rule(nq), uploaded once per device and nq.  The copy is synchronous, as _corr_tables' is: the table is shared by every
+        plan and stream, and none may see a copy in flight."""
+        key = (str(dev), int(nq))
+        tab = _HERMITE_NODES.get(key)
+        if tab is None:
+            tab = torch.from_numpy(np.stack(hermite_rule(nq))).to(dev).contiguous()
+            torch.cuda.synchronize(dev)
+            _HERMITE_NODES[key] = tab
+        return tab
+
+    def _hermite_tables(self, r, op, sfx, stream, vx, vy, n1, n2, hw, same, ntk, like):
+        """The workspace of one hermite launch: the coefficient tables [order + 1][n·hw] of the
+        variance maps vx ([n1, hw]) and vy ([n2, hw]; not with ``same``, where yy holds xx's
+        values and the x tables serve both), and the tables of φ' with ``ntk``, written by
+        cgp_hermite_coef_* on ``stream`` and set in the record ``r`` (cgp_hermite_args or
+        cgp_hermite_cov_args).  (n1 + n2)·(order + 1)·hw values, n1·… with same, twice that
+        with ntk.  Returns the workspace: the caller keeps it until the launch is enqueued."""
+        phi, order, nq = op.rule
+        nodes = self._hermite_nodes(like.device, nq)
+        sides = [(vx, n1 * hw)] if same else [(vx, n1 * hw), (vy, n2 * hw)]
+        ws = torch.empty(((2 if ntk else 1) * (order + 1) * sum(c for _, c in sides),),
+                         dtype=like.dtype, device=like.device)
+        item, at, tabs = ws.element_size(), ws.data_ptr(), []
+        for v, count in sides:
+            c = N.HermiteCoefArgs()
+            c.var, c.nodes, c.count = v.data_ptr(), nodes.data_ptr(), count
+            c.phi, c.order, c.nq = phi, order, nq
+            c.a = at
+            at += (order + 1) * count * item
+            if ntk:
+                c.da = at
+                at += (order + 1) * count * item
+            N.check(getattr(N.load(), f"cgp_hermite_coef_{sfx}")(c, stream), "cgp_hermite_coef")
+            tabs.append((c.a, c.da, count))
+        (r.ax, r.dax, r.stride_x), (r.ay, r.day, r.stride_y) = tabs[0], tabs[-1]
+        r.order = order
+        return ws
 
     @staticmethod
     def _conv_args(op, src, out, nmaps, n1, n2, same=0, diag=0, flags=0, bias=None, addend=None,
@@ -1152,8 +1244,11 @@ class Plan:
             elif op.kind in NONLIN_KINDS:
                 xin, yin = vals[op.src]
                 buf = torch.empty((n1 + n2, ho, wo), dtype=xx0.dtype, device=dev)
+                extra = NONLIN_CALLS[op.kind][4](op)
+                if op.kind == "hermite":
+                    extra += (N.ptr(self._hermite_nodes(dev, op.rule[2])),)
                 N.call(f"cgp_var_{op.kind}_{sfx}", N.ptr(xin), N.ptr(yin), n1, n2, ho * wo,
-                       int(same), *NONLIN_CALLS[op.kind][4](op), N.ptr(buf[:n1]),
+                       int(same), *extra, N.ptr(buf[:n1]),
                        N.ptr(buf[n1:]), stream)
                 out = (buf[:n1], buf[n1:])
             elif op.kind == "add":
@@ -1561,6 +1656,15 @@ class Plan:
                         what = "cgp_sin_cov"
                         r = pairwise(maps(N.SinCovArgs(), st), st)
                         r.A, r.B, r.C, r.D = st.op.consts
+                    elif st.fn in ("hermite", "hermite_ntk"):
+                        what = "cgp_hermite_cov"
+                        r = pairwise(maps(N.HermiteCovArgs(), st), st)
+                        # the tables of every image of the variance maps, per launch: a map
+                        # filled chunk by chunk (run_self_variances) changes between chunks
+                        vx, vy = var[st.var]
+                        ws = self._hermite_tables(  # noqa: F841 (alive until the launch)
+                            r, st.op, sfx, stream, vx, vy, vx.shape[0], vy.shape[0],
+                            r.h * r.w, same, ntk, x)
                     elif st.fn == "avgpool":
                         what = "cgp_covmap_avgpool"
                         r = maps(N.CovAvgPoolArgs(), st)

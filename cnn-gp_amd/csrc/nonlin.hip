@@ -1,7 +1,9 @@
 // nonlin.hip — the entry points of every nonlinearity: ReLU, erf, GELU, the two-slope ReLU
-// and the sinusoid on pair maps (cgp_relu_*, cgp_relu_ntk_*, cgp_erf_*, cgp_gelu_*,
-// cgp_abrelu_*, cgp_sin_*), on the per-image variances (cgp_var_*) and on position-pair maps
-// (cgp_cov_nonlin_*, cgp_covntk_nonlin_*, cgp_gelu_cov_*, cgp_abrelu_cov_*, cgp_sin_cov_*).  The kernels and the maps are
+// the sinusoid and the Hermite series on pair maps (cgp_relu_*, cgp_relu_ntk_*, cgp_erf_*,
+// cgp_gelu_*, cgp_abrelu_*, cgp_sin_*, cgp_hermite_*), on the per-image variances (cgp_var_*)
+// and on position-pair maps (cgp_cov_nonlin_*, cgp_covntk_nonlin_*, cgp_gelu_cov_*,
+// cgp_abrelu_cov_*, cgp_sin_cov_*, cgp_hermite_cov_*), and the series' coefficient kernel
+// (cgp_hermite_coef_*).  The kernels and the maps are
 // nonlin_walk.h's; here each layout has one check and one launch, named by the entry point
 // for the messages.  Every check returns CGP_EINVAL before any HIP call.
 
@@ -40,6 +42,70 @@ SinMap<T> sin_map(double A, double B, double C, double D) {
     return SinMap<T>{(T)A, (T)B, (T)C, (T)D};
 }
 
+// the Hermite series' order and tables (cgp_hermite_args / cgp_hermite_cov_args): n1h / n2h are
+// the least strides, 1 where the entry point does not know the buffers' image counts
+template <class A>
+int hermite_check(const char* name, const A* a, bool need_y, long long n1h, long long n2h) {
+    if (a->order < 1 || a->order > CGP_HERMITE_MAX_ORDER)
+        return fail(CGP_EINVAL, "%s: order %d is not in [1, %d]", name, a->order,
+                    CGP_HERMITE_MAX_ORDER);
+    if (!a->ax || (need_y && !a->ay) || (a->theta && (!a->dax || (need_y && !a->day))))
+        return fail(CGP_EINVAL, "%s: NULL coefficient table", name);
+    if (a->stride_x < n1h || (need_y && a->stride_y < n2h))
+        return fail(CGP_EINVAL, "%s: table stride below the variance buffer's size", name);
+    return CGP_OK;
+}
+template <typename T, class A>
+HermiteMap<T> hermite_map(const A* a) {
+    return HermiteMap<T>{static_cast<const T*>(a->ax),  static_cast<const T*>(a->ay),
+                         static_cast<const T*>(a->dax), static_cast<const T*>(a->day),
+                         static_cast<const T*>(a->xx),  static_cast<const T*>(a->yy),
+                         a->stride_x, a->stride_y, a->order};
+}
+
+int hermite_rule_check(const char* name, int phi, int order, int nq, const double* nodes) {
+    if (phi < CGP_HERMITE_TANH || phi > CGP_HERMITE_GELU)
+        return fail(CGP_EINVAL, "%s: phi %d is not a CGP_HERMITE_* id", name, phi);
+    if (order < 1 || order > CGP_HERMITE_MAX_ORDER)
+        return fail(CGP_EINVAL, "%s: order %d is not in [1, %d]", name, order,
+                    CGP_HERMITE_MAX_ORDER);
+    if (nq <= order || nq > CGP_HERMITE_MAX_NODES)
+        return fail(CGP_EINVAL, "%s: %d nodes are not in (order, %d]", name, nq,
+                    CGP_HERMITE_MAX_NODES);
+    if (!nodes) return fail(CGP_EINVAL, "%s: NULL node table", name);
+    return CGP_OK;
+}
+
+// one launch of the coefficient kernel in the order's bucket; da: grid y = 2
+template <typename T>
+int hermite_coef_launch(const HermiteCoefP<T>& p, void* stream) {
+    const dim3 grid((unsigned)((p.count + kWalkBlock - 1) / kWalkBlock), p.da ? 2 : 1);
+    const dim3 block(kWalkBlock);
+    hipStream_t s = as_stream(stream);
+    if (p.order <= 8)
+        hipLaunchKernelGGL((hermite_coef_kernel<T, 8>), grid, block, 0, s, p);
+    else if (p.order <= 16)
+        hipLaunchKernelGGL((hermite_coef_kernel<T, 16>), grid, block, 0, s, p);
+    else if (p.order <= 32)
+        hipLaunchKernelGGL((hermite_coef_kernel<T, 32>), grid, block, 0, s, p);
+    else
+        hipLaunchKernelGGL((hermite_coef_kernel<T, 64>), grid, block, 0, s, p);
+    return check_launch("hermite_coef_kernel");
+}
+
+template <typename T>
+int hermite_coef_impl(const cgp_hermite_coef_args* a, void* stream) {
+    if (!a || !a->var || !a->a) return fail(CGP_EINVAL, "hermite_coef: NULL argument");
+    if (a->count <= 0 || a->count >= (1LL << 31))
+        return fail(CGP_EINVAL, "hermite_coef: bad sizes");
+    if (int e = hermite_rule_check("hermite_coef", a->phi, a->order, a->nq, a->nodes)) return e;
+    return hermite_coef_launch(
+        HermiteCoefP<T>{static_cast<const T*>(a->var), static_cast<T*>(a->a),
+                        static_cast<T*>(a->da), nullptr, a->nodes, a->count, a->phi, a->order,
+                        a->nq},
+        stream);
+}
+
 // ----------------------------------------------------------------------------------
 // the layer path.  theta == NULL is the forward-only form.
 // ----------------------------------------------------------------------------------
@@ -54,7 +120,7 @@ struct PairArgs {
     int64_t nmaps, n1, n2;
     int32_t hw, same, diag;
 };
-// of cgp_erf_args, cgp_gelu_args, cgp_abrelu_args, cgp_sin_args; a NULL record gives NULL fields
+// of cgp_erf_args, cgp_gelu_args, cgp_abrelu_args, cgp_sin_args, cgp_hermite_args; a NULL record gives NULL fields
 template <class A>
 PairArgs pair_args(const A* a) {
     if (!a) return PairArgs{};
@@ -165,6 +231,15 @@ int sin_impl(const cgp_sin_args* a, void* stream) {
     if (int e = sin_check("sin", a->A, a->B, a->C, a->D)) return e;
     return pair_launch<T>(c, sin_map<T>(a->A, a->B, a->C, a->D), stream);
 }
+template <typename T>
+int hermite_impl(const cgp_hermite_args* a, void* stream) {
+    const PairArgs c = pair_args(a);
+    if (int e = pair_check("hermite", c)) return e;
+    if (int e = hermite_check("hermite", a, !(a->same && a->diag), a->n1 * a->hw,
+                              a->n2 * a->hw))
+        return e;
+    return pair_launch<T>(c, hermite_map<T>(a), stream);
+}
 
 // ----------------------------------------------------------------------------------
 // the per-image variances
@@ -215,6 +290,23 @@ int var_sin_impl(const VarArgs<T>& a, double A, double B, double C, double D, vo
     return var_launch(a, sin_map<T>(A, B, C, D), stream);
 }
 
+// the coefficient kernel with var_out: xx -> xo, then (same ? xx : yy) -> yo
+template <typename T>
+int var_hermite_impl(const VarArgs<T>& a, int phi, int order, int nq, const double* nodes,
+                     void* stream) {
+    if (int e = var_check("var_hermite", a)) return e;
+    if (int e = hermite_rule_check("var_hermite", phi, order, nq, nodes)) return e;
+    if (a.n1 * a.hw >= (1LL << 31) || a.n2 * a.hw >= (1LL << 31))
+        return fail(CGP_EINVAL, "var_hermite: bad sizes");
+    if (int e = hermite_coef_launch(HermiteCoefP<T>{a.xx, nullptr, nullptr, a.xo, nodes,
+                                                    a.n1 * a.hw, phi, order, nq},
+                                    stream))
+        return e;
+    return hermite_coef_launch(HermiteCoefP<T>{a.same ? a.xx : a.yy, nullptr, nullptr, a.yo,
+                                               nodes, a.n2 * a.hw, phi, order, nq},
+                               stream);
+}
+
 // ----------------------------------------------------------------------------------
 // position-pair maps.  theta == NULL is the forward-only form.
 // ----------------------------------------------------------------------------------
@@ -232,7 +324,7 @@ struct CovArgs {
     int64_t npairs;
     int32_t h, w, same;
 };
-// of cgp_covntk_nonlin_args, cgp_abrelu_cov_args, cgp_sin_cov_args; a NULL record gives NULL fields
+// of cgp_covntk_nonlin_args, cgp_abrelu_cov_args, cgp_sin_cov_args, cgp_hermite_cov_args; a NULL record gives NULL fields
 template <class A>
 CovArgs cov_args(const A* a) {
     if (!a) return CovArgs{};
@@ -342,6 +434,15 @@ int sin_cov_impl(const cgp_sin_cov_args* a, void* stream) {
     if (int e = sin_check("sin_cov", a->A, a->B, a->C, a->D)) return e;
     return cov_launch<T>("sin_cov", c, sin_map<T>(a->A, a->B, a->C, a->D), stream);
 }
+template <typename T>
+int hermite_cov_impl(const cgp_hermite_cov_args* a, void* stream) {
+    const CovArgs c = cov_args(a);
+    if (int e = cov_check("hermite_cov", c)) return e;
+    if (int e = hermite_check("hermite_cov", a, true, (long long)a->h * a->w,
+                              (long long)a->h * a->w))
+        return e;
+    return cov_launch<T>("hermite_cov", c, hermite_map<T>(a), stream);
+}
 
 }  // namespace
 
@@ -358,6 +459,9 @@ size_t cgp_gelu_cov_args_size(void) { return sizeof(cgp_gelu_cov_args); }
 size_t cgp_abrelu_cov_args_size(void) { return sizeof(cgp_abrelu_cov_args); }
 size_t cgp_sin_args_size(void) { return sizeof(cgp_sin_args); }
 size_t cgp_sin_cov_args_size(void) { return sizeof(cgp_sin_cov_args); }
+size_t cgp_hermite_coef_args_size(void) { return sizeof(cgp_hermite_coef_args); }
+size_t cgp_hermite_args_size(void) { return sizeof(cgp_hermite_args); }
+size_t cgp_hermite_cov_args_size(void) { return sizeof(cgp_hermite_cov_args); }
 
 #define CGP_NONLIN_ENTRY(name, impl, args)                                                \
     int name##_f64(const args* a, void* stream) { return impl<double>(a, stream); }       \
@@ -373,6 +477,9 @@ CGP_NONLIN_ENTRY(cgp_gelu_cov, gelu_cov_impl, cgp_gelu_cov_args)
 CGP_NONLIN_ENTRY(cgp_abrelu_cov, abrelu_cov_impl, cgp_abrelu_cov_args)
 CGP_NONLIN_ENTRY(cgp_sin, sin_impl, cgp_sin_args)
 CGP_NONLIN_ENTRY(cgp_sin_cov, sin_cov_impl, cgp_sin_cov_args)
+CGP_NONLIN_ENTRY(cgp_hermite_coef, hermite_coef_impl, cgp_hermite_coef_args)
+CGP_NONLIN_ENTRY(cgp_hermite, hermite_impl, cgp_hermite_args)
+CGP_NONLIN_ENTRY(cgp_hermite_cov, hermite_cov_impl, cgp_hermite_cov_args)
 #undef CGP_NONLIN_ENTRY
 
 #define CGP_VAR_ENTRY(name, T, sfx, Map)                                                   \
@@ -409,5 +516,17 @@ int cgp_var_abrelu_f32(const float* xx, const float* yy, int64_t n1, int64_t n2,
 CGP_VAR_SIN_ENTRY(double, f64)
 CGP_VAR_SIN_ENTRY(float, f32)
 #undef CGP_VAR_SIN_ENTRY
+
+// the series' rule (phi, order, nq, nodes) stands between `same` and the outputs
+#define CGP_VAR_HERMITE_ENTRY(T, sfx)                                                        \
+    int cgp_var_hermite_##sfx(const T* xx, const T* yy, int64_t n1, int64_t n2, int32_t hw,  \
+                              int32_t same, int32_t phi, int32_t order, int32_t nq,          \
+                              const double* nodes, T* xx_out, T* yy_out, void* stream) {     \
+        return var_hermite_impl(VarArgs<T>{xx, yy, n1, n2, hw, same, xx_out, yy_out}, phi,   \
+                                order, nq, nodes, stream);                                   \
+    }
+CGP_VAR_HERMITE_ENTRY(double, f64)
+CGP_VAR_HERMITE_ENTRY(float, f32)
+#undef CGP_VAR_HERMITE_ENTRY
 
 }  // extern "C"

@@ -146,6 +146,164 @@ struct SinMap {
     __device__ __forceinline__ T var(T v) const { return A * (T(1) - ces(T(4) * v)); }
 };
 
+// Any smooth φ by its Hermite (Mehler) series: with ρ = c/√(v1·v2) and the
+// coefficients a_n(v) = E_z[φ(√v·z)·h_n(z)], h_n = He_n/√n!, of each image pixel,
+//   K' = Σ_{n<=N} a_n(v1)·a_n(v2)·ρⁿ     κ̇ = Σ_{n<=N} a'_n(v1)·a'_n(v2)·ρⁿ     (a' of φ')
+// and v' = Σ a_n(v)², κ̇ = Σ a'_n(v)² where the ReLU overrides: the series at ρ = 1, so the
+// diagonal is the kernel's own.  The coefficients come from hermite_coef_kernel as tables
+// [n][image·hw + pixel] over the variance buffer: a pixel's offset into a table is its
+// variance's offset from the buffer's base, no division, and a wave's loads for one n are
+// contiguous in the pixel.  ρ is 0 where v1·v2 is not positive (a zero-variance pixel has
+// a_n = 0 for n >= 1: the series is a_0·a_0, exact) and is clamped to [−1, 1], NaN kept.  The
+// series is summed by Horner from n = N down, one fma per term on the rounded product, so
+// pair(x, y) and pair(y, x) are the same bits.  There is no var(): the variances need the
+// coefficients (cgp_var_hermite_*).
+template <typename T>
+struct HermiteMap {
+    const T *ax, *ay, *dax, *day;   // tables of a and a' of xx and of yy; a' read with NTK
+    const T *xb, *yb;               // the variance buffers the walk's vx / vy point into
+    long long sx, sy;               // elements between two n of the x and of the y tables
+    int N;
+    // Σ a_n², n = N down to 0
+    __device__ __forceinline__ T sumsq(const T* a, long long s) const {
+        T acc = T(0);
+        for (int n = N; n >= 0; --n) {
+            const T t = a[n * s];
+            acc = fma_t(t, t, acc);
+        }
+        return acc;
+    }
+    __device__ __forceinline__ T series(const T* a, long long s, const T* b, long long sb,
+                                        T rho) const {
+        T acc = T(0);
+        for (int n = N; n >= 0; --n) {
+            const T t = a[n * s] * b[n * sb];
+            acc = fma_t(acc, rho, t);
+        }
+        return acc;
+    }
+    template <bool NTK>
+    __device__ __forceinline__ T pair(T c, const T* vx, const T* vy, bool self, T& kdot) const {
+        const long long ox = vx - xb;
+        if (self) {
+            if constexpr (NTK) kdot = sumsq(dax + ox, sx);
+            return sumsq(ax + ox, sx);                       // xy' = xx'
+        }
+        const long long oy = vy - yb;
+        const T t = *vx * *vy;
+        T rho = t > T(0) ? c / sqrt_t(t) : T(0);
+        rho = rho > T(1) ? T(1) : rho;                       // NaN kept
+        rho = rho < T(-1) ? T(-1) : rho;
+        if constexpr (NTK) kdot = series(dax + ox, sx, day + oy, sy, rho);
+        return series(ax + ox, sx, ay + oy, sy, rho);
+    }
+};
+
+// φ and φ' of the series, chosen by a launch-uniform id (CGP_HERMITE_*: cnngp.h), in double.
+// σ(x) is evaluated on the side where exp does not overflow; 1 − σ(x) is σ(−x).
+__device__ __forceinline__ double hermite_sigmoid(double x) {
+    const double e = exp(-fabs_t(x));
+    const double s = 1.0 / (1.0 + e);
+    return x >= 0 ? s : e * s;
+}
+__device__ __forceinline__ double hermite_phi(int id, bool deriv, double x) {
+    constexpr double kS2pi = 0.79788456080286535588;         // √(2/π)
+    constexpr double kRs2 = 0.70710678118654752440;          // 1/√2
+    constexpr double kRs2pi = 0.39894228040143267794;        // 1/√(2π)
+    switch (id) {
+        case 0: {                                            // tanh
+            const double t = tanh(x);
+            return deriv ? 1.0 - t * t : t;
+        }
+        case 1: {                                            // sigmoid
+            const double s = hermite_sigmoid(x);
+            return deriv ? s * hermite_sigmoid(-x) : s;
+        }
+        case 2:                                              // softplus log(1 + eˣ)
+            return deriv ? hermite_sigmoid(x)
+                         : log1p(exp(-fabs_t(x))) + (x > 0 ? x : 0.0);
+        case 3: {                                            // SiLU x·σ(x)
+            const double s = hermite_sigmoid(x);
+            return deriv ? s * (1.0 + x * hermite_sigmoid(-x)) : x * s;
+        }
+        case 4: {                                            // GELU's tanh approximation
+            const double x2 = x * x;
+            const double t = tanh(kS2pi * x * (1.0 + 0.044715 * x2));
+            return deriv ? 0.5 * (1.0 + t) +
+                               0.5 * x * (1.0 - t * t) * kS2pi * (1.0 + 3.0 * 0.044715 * x2)
+                         : 0.5 * x * (1.0 + t);
+        }
+        case 5:                                              // erf
+            return deriv ? 2.0 * kS2pi * kRs2 * exp(-x * x) : erf(x);
+        default: {                                           // GELU x·Φ(x)
+            const double cdf = 0.5 * (1.0 + erf(x * kRs2));
+            return deriv ? cdf + x * kRs2pi * exp(-0.5 * x * x) : x * cdf;
+        }
+    }
+}
+
+// The coefficients of `count` variances (image pixels): a Q-node Gauss–Hermite rule per pixel
+// with the N + 1 accumulators in registers (NMAX: the order's bucket, so the array is indexed
+// at compile time), in double whatever T is.  nodes: [2][nq], z_q then w_q, Σ w_q = 1.  h_n by
+// h_{n+1} = (z·h_n − √n·h_{n−1})/√(n+1).  blockIdx.y = 1 is the table of φ'.  With var_out
+// (grid y = 1) no table is written: var_out = Σ a_n² of the coefficients rounded to T, the
+// bits HermiteMap's override returns.
+template <typename T>
+struct HermiteCoefP {
+    const T* var;
+    T* a;
+    T* da;
+    T* var_out;
+    const double* nodes;
+    long long count;
+    int phi, order, nq;
+};
+
+template <typename T, int NMAX>
+__global__ __launch_bounds__(kWalkBlock) void hermite_coef_kernel(const HermiteCoefP<T> p) {
+    const long long e = (long long)blockIdx.x * kWalkBlock + threadIdx.x;
+    if (e >= p.count) return;
+    const bool deriv = blockIdx.y != 0;
+    double v = (double)p.var[e];
+    v = v < 0.0 ? 0.0 : v;                                   // NaN kept
+    const double s = __builtin_sqrt(v);
+    double acc[NMAX + 1];
+#pragma unroll
+    for (int n = 0; n <= NMAX; ++n) acc[n] = 0.0;
+    for (int q = 0; q < p.nq; ++q) {
+        const double z = p.nodes[q];
+        const double f = p.nodes[p.nq + q] * hermite_phi(p.phi, deriv, s * z);
+        double h0 = 1.0, h1 = z;
+        acc[0] += f;
+        acc[1] = fma_t(f, h1, acc[1]);
+#pragma unroll
+        for (int n = 1; n < NMAX; ++n) {
+            // √n and 1/√(n+1) fold to constants in the unrolled loop: no division per node
+            const double h2 = (z * h1 - __builtin_sqrt((double)n) * h0) *
+                              (1.0 / __builtin_sqrt((double)(n + 1)));
+            acc[n + 1] = fma_t(f, h2, acc[n + 1]);
+            h0 = h1;
+            h1 = h2;
+        }
+    }
+    if (p.var_out) {
+        T sum = T(0);
+#pragma unroll
+        for (int n = NMAX; n >= 0; --n) {
+            if (n <= p.order) {
+                const T t = (T)acc[n];
+                sum = fma_t(t, t, sum);
+            }
+        }
+        p.var_out[e] = sum;
+        return;
+    }
+    T* tab = deriv ? p.da : p.a;
+#pragma unroll
+    for (int n = 0; n <= NMAX; ++n)
+        if (n <= p.order) tab[n * p.count + e] = (T)acc[n];
+}
+
 // The post-stage of the conv kernels on position-pair maps (covpool.hip, covntk.hip): the map
 // of run-time `kind` at (c, v1, v2) = (S[p, q], xx_i[p], yy_j[q]).  The override applies where
 // same, i == j and p == q.  The forward conv has no GELU post-stage (cgp_cov_conv_* rejects

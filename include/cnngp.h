@@ -809,6 +809,127 @@ int cgp_sin_cov_f64(const cgp_sin_cov_args* args, void* stream);
 int cgp_sin_cov_f32(const cgp_sin_cov_args* args, void* stream);
 
 /*
+ * Any smooth φ by its Hermite (Mehler) series (additions to ABI 12: no struct or existing
+ * entry point changed; no reference counterpart): tanh, sigmoid, softplus, SiLU,
+ * GELU's tanh approximation, and erf and the exact GELU as cross-checks of cgp_erf_* and
+ * cgp_gelu_*.  In the conventions of the ReLU entry points above -- per pixel (xy, xx, yy) =
+ * (c, v1, v2), no rescaling.  With h_n = He_n/√n! and z ~ N(0, 1),
+ *   a_n(v)  = E_z[φ(√v·z)·h_n(z)],   a'_n(v) = E_z[φ'(√v·z)·h_n(z)]    n = 0 .. order
+ *   ρ       = c/√(v1·v2), 0 where v1·v2 is not positive, clamped to [-1, 1] (a NaN is kept)
+ *   pair map    out_xy = Σ_n a_n(v1)·a_n(v2)·ρⁿ
+ *   variances   v' = Σ_n a_n(v)²: the truncated sum, the pair map at ρ = 1, not E φ²
+ *   NTK         out_theta = theta·κ̇,  κ̇ = Σ_n a'_n(v1)·a'_n(v2)·ρⁿ = ∂out_xy/∂c
+ * Where cgp_relu_* overrides its map (same && !diag: pairs i == j; same && diag: all), out_xy
+ * = v'[i], the same bits cgp_var_hermite_* writes, and κ̇ = Σ_n a'_n(v)².  The series is summed
+ * by Horner from n = order down, one fma per term on the rounded product of the two
+ * coefficients, so the map is symmetric in its two images bit for bit.
+ *
+ * cgp_hermite_coef_* computes the coefficients of `count` variances (every pixel of every
+ * image of a variance buffer) by a Gauss–Hermite rule of nq nodes, in double whatever the
+ * type, and stores them rounded once as tables a[n][count] (and da[n][count] of φ' when da is
+ * not NULL).  nodes: device double [2][nq], the nodes z_q and then the weights w_q of a rule
+ * for the standard normal, E_z[f(z)] = Σ_q w_q·f(z_q): the package uploads the probabilists'
+ * Gauss–Hermite rule (numpy.polynomial.hermite_e.hermegauss, weights over √(2π)) compressed to
+ * |z| <= 12.5 (program.hermite_rule).  A negative variance counts as 0.  1 <= order <= CGP_HERMITE_MAX_ORDER, order < nq <= CGP_HERMITE_MAX_NODES, count <
+ * 2^31; otherwise CGP_EINVAL.
+ */
+#define CGP_HERMITE_TANH 0
+#define CGP_HERMITE_SIGMOID 1
+#define CGP_HERMITE_SOFTPLUS 2
+#define CGP_HERMITE_SILU 3
+#define CGP_HERMITE_GELU_TANH 4
+#define CGP_HERMITE_ERF 5
+#define CGP_HERMITE_GELU 6
+#define CGP_HERMITE_MAX_ORDER 64
+#define CGP_HERMITE_MAX_NODES 256
+typedef struct cgp_hermite_coef_args {
+    const void* var;        /* [count] variances */
+    void* a;                /* [order + 1][count] */
+    void* da;               /* [order + 1][count], or NULL: no table of φ' */
+    const double* nodes;    /* device [2][nq] */
+    int64_t count;
+    int32_t phi;            /* CGP_HERMITE_* */
+    int32_t order, nq;
+    int32_t flags;          /* ignored */
+} cgp_hermite_coef_args;
+size_t cgp_hermite_coef_args_size(void);
+int cgp_hermite_coef_f64(const cgp_hermite_coef_args* args, void* stream);
+int cgp_hermite_coef_f32(const cgp_hermite_coef_args* args, void* stream);
+/*
+ * The series on pair maps.  cgp_hermite_args has the fields and the rules of cgp_erf_args
+ * (theta == NULL is the forward-only pass; in-place is allowed, and theta may be xy itself;
+ * addend is added to out_xy only, as a separate rounding; same or diag need n1 == n2; hw is at
+ * most 2048; nmaps < 2^31), then the tables: ax / ay of the images of xx / yy (cgp_hermite_coef_*
+ * over [n1·hw] and over [n2·hw] variances, or one call over a buffer that holds both), dax /
+ * day with theta, and stride_x / stride_y, the elements between two n of each table (that
+ * call's count), at least n1·hw and n2·hw.  ay may be ax where yy holds xx's values (same);
+ * ay and day are not read when same && diag.
+ */
+typedef struct cgp_hermite_args {
+    const void* xy;         /* [nmaps][hw] */
+    const void* theta;      /* [nmaps][hw] or NULL */
+    void* out_xy;           /* [nmaps][hw] */
+    void* out_theta;        /* [nmaps][hw] (unused when theta is NULL) */
+    const void* addend;     /* [nmaps][hw] or NULL */
+    const void* xx;         /* [n1][hw] variances at the nonlinearity's input */
+    const void* yy;         /* [n2][hw] (may be NULL when same && diag) */
+    int64_t nmaps, n1, n2;
+    int32_t hw, same, diag;
+    int32_t flags;          /* ignored */
+    const void* ax;         /* [order + 1][stride_x] */
+    const void* ay;         /* [order + 1][stride_y] */
+    const void* dax;        /* like ax, of φ' (unused when theta is NULL) */
+    const void* day;
+    int64_t stride_x, stride_y;
+    int32_t order;
+    int32_t reserved;
+} cgp_hermite_args;
+size_t cgp_hermite_args_size(void);
+int cgp_hermite_f64(const cgp_hermite_args* args, void* stream);
+int cgp_hermite_f32(const cgp_hermite_args* args, void* stream);
+/* The series on the per-image variances: xx' = Σ_n a_n(xx)²; yy' = xx' if same else the same
+ * of yy.  xx: [n1][hw], yy: [n2][hw].  It runs the coefficient kernel itself and squares and
+ * sums the rounded coefficients in registers; no table is written. */
+int cgp_var_hermite_f64(const double* xx, const double* yy, int64_t n1, int64_t n2, int32_t hw,
+                        int32_t same, int32_t phi, int32_t order, int32_t nq,
+                        const double* nodes, double* xx_out, double* yy_out, void* stream);
+int cgp_var_hermite_f32(const float* xx, const float* yy, int64_t n1, int64_t n2, int32_t hw,
+                        int32_t same, int32_t phi, int32_t order, int32_t nq,
+                        const double* nodes, float* xx_out, float* yy_out, void* stream);
+/*
+ * The series on position-pair maps, one entry point for both runs, with cgp_sin_cov_*'s
+ * fields and rules (the element rule, the override where same, pair_i[m] == pair_j[m] and
+ * p == q, in-place, the addends), then the tables as in cgp_hermite_args: over the whole
+ * buffers xx and yy, whatever images the pairs name.
+ */
+typedef struct cgp_hermite_cov_args {
+    const void* in;            /* [npairs][h][h][w][w] */
+    const void* theta;         /* like in, or NULL: the forward-only pass */
+    void* out;
+    void* out_theta;           /* (unused when theta is NULL) */
+    const void* addend;        /* like out, or NULL */
+    const void* addend_theta;  /* like out_theta, or NULL */
+    const void* xx;            /* [n1][h][w] variances at the nonlinearity's input */
+    const void* yy;            /* [n2][h][w] (same: may be xx) */
+    const int32_t* pair_i;     /* device [npairs] */
+    const int32_t* pair_j;
+    int64_t npairs;
+    int32_t h, w;
+    int32_t same;
+    int32_t flags;             /* ignored */
+    const void* ax;            /* [order + 1][stride_x] */
+    const void* ay;            /* [order + 1][stride_y] */
+    const void* dax;           /* like ax, of φ' (unused when theta is NULL) */
+    const void* day;
+    int64_t stride_x, stride_y;
+    int32_t order;
+    int32_t reserved;
+} cgp_hermite_cov_args;
+size_t cgp_hermite_cov_args_size(void);
+int cgp_hermite_cov_f64(const cgp_hermite_cov_args* args, void* stream);
+int cgp_hermite_cov_f32(const cgp_hermite_cov_args* args, void* stream);
+
+/*
  * out = alpha·a + beta·b (b may be NULL: out = alpha·a), n elements.  The unfused form
  * of Sum (alpha = beta = 1, kernel_patch.py:43-63) and Mixture (kernels.py:220-225).
  * Products and the sum are rounded separately (no FMA contraction), like torch.
